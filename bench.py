@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput of the FastSpeech2 feature-prediction train step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 With N > 1 and no launcher environment (WORLD_SIZE unset) this process starts the N ranks itself -- before it makes
 any GPU call -- and only relays their output; under ``python -m torch.distributed.run --nproc-per-node N`` each
@@ -10,16 +10,22 @@ process is one rank (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environm
 One "step" = forward + all losses + backward + gradient exchange (N > 1) + clip + fused AdamW on one
 synthetic LJSpeech-shaped batch of 32 utterances per GPU (BASELINE.json configs[1]: fp32, batch 32,
 ~100-128 phonemes, 80 x ~600 mel), dropout ON as in training, inputs resident in HBM before the
-timed region.  ``value`` = real (unpadded) mel frames processed per second by the whole job.
+timed region.  ``value`` = real (unpadded) mel frames processed per second by the whole job; ``ms_per_step`` = one
+timed step.  The K timed steps are the first K optimizer steps from the seeded initial state (model, optimizer, dropout
+stream and BatchNorm statistics are reset after warm-up and tuning), so with the same arguments they compute the same
+thing in every run: ``--dump-outputs DIR`` writes what the last of them computed (loss terms, the forward outputs, a
+fixed sample of the updated parameters and of the gradient) as DIR/<name>.npy.
 
-The JSON line also carries
+A plain run does only that, with the tile tuner's in-step stage cut off at PLAIN_TUNING_UNTIL_S after start.  ``--full``
+runs the whole stage and adds the secondary measurements to the JSON line (null without it):
   roofline     : the dominant kernel (fp32 MFMA GEMM family) -- algorithmic FLOPs per launch / average
                  launch duration, measured live with HIP events on the launch stream, against the
                  157.3 TFLOP/s fp32 matrix peak;
   cpu_baseline : the CPU oracle (pure-PyTorch restatement of the reference, ``oracle/``) timed on this
                  box's host cores on a bounded sample of the same workload (rank 0, N = 1 only);
   split_fp32, bf16_mixed_b64, learn_alignment : the same step in the other configurations of BASELINE.json / the
-                 reference (N = 1, default flags only; >= 20 timed steps each) -- reported beside ``value``, never as it.
+                 reference (N = 1, default flags only; >= 20 timed steps each) -- reported beside ``value``, never as it;
+  host_enqueue_ms_per_step : the host's own cost of one step (one step into an empty queue, median of 9).
 """
 from __future__ import annotations
 
@@ -29,6 +35,8 @@ import os
 import sys
 import time
 from pathlib import Path
+
+T_START = time.perf_counter()
 
 # before the HIP runtime initialises (fastspeech2_lightning_amd/hip.py explains): with the default 4 hardware queues the
 # step's side stream shares a queue with the main stream once RCCL has made its own streams.  Not for the gloo rehearsal
@@ -58,11 +66,15 @@ def host_cores() -> int:
     return max(1, min(n, int(os.environ.get("FS2_BENCH_CPU_THREADS", 16))))
 
 
+#: seconds after start past which a plain run tries no further tile in the tuner's in-step stage: set-up, warm-up and
+#: tuning of a plain run must stay within 30 s (torch import and model build take ~15 of them), the timed steps excluded
+PLAIN_TUNING_UNTIL_S = 20.0
+#: --dump-outputs: at most this many bytes in all; a larger array is written as a fixed, seeded sample of its elements
+DUMP_BUDGET_BYTES = 64 << 20
+
+
 def log(msg):
     print(f"[bench +{time.perf_counter() - T_START:7.1f}s] {msg}", file=sys.stderr, flush=True)
-
-
-T_START = time.perf_counter()
 
 
 def make_config(learn_alignment=False, gst=False):
@@ -163,10 +175,17 @@ def spawn_ranks(n: int) -> int:
     return code
 
 
+def _positive(text):
+    n = int(text)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, got {n}")
+    return n
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200,
+    ap.add_argument("--steps", type=_positive, default=200,
                     help="timed steps (default 200 = ~4 s: long enough for clocks and the driver's activity sampler)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--dry-run", action="store_true",
@@ -191,6 +210,11 @@ def build_parser():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--learn-alignment", action="store_true",
                     help="reference default config: jointly learned alignment (aligner + MAS + CTC/bin losses)")
+    ap.add_argument("--full", action="store_true",
+                    help="the whole in-step tile stage and the secondary measurements (roofline, CPU baseline, the other "
+                         "configurations, host enqueue cost); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     return ap
 
 
@@ -236,6 +260,23 @@ class Rig:
         self.main_stream = None
         if os.environ.get("FS2_BENCH_MAIN_PRIORITY") == "high":
             self.main_stream = torch.cuda.Stream(device=f"cuda:{local}", priority=torch.cuda.Stream.priority_range()[1])
+        self.initial_state = self._training_state(clone=True)
+
+    def _training_state(self, clone=False):
+        """Everything a step reads and the optimizer step writes: parameters, gradient, Adam moments, the optimizer's device
+        record (step count: learning rate, bias corrections and the dropout masks follow it), BatchNorm statistics."""
+        S = self.model.store
+        ts = [S.flat, S.grad, S.adam_m, S.adam_v, self.model.step_state, S.bn_counters]
+        ts += [t for n, t in S.buffers.items() if not n.endswith("num_batches_tracked")]  # (those are views of bn_counters)
+        return [t.clone() for t in ts] if clone else ts
+
+    def reset_training_state(self):
+        """Back to the seeded initial state, in place (recorded launch plans keep their addresses): the timed steps then
+        compute the same thing however many steps warm-up and tuning took."""
+        for dst, src in zip(self._training_state(), self.initial_state):
+            dst.copy_(src)
+        self.model.store.weights_changed()
+        torch.cuda.synchronize()
 
     def step(self):
         if self.main_stream is not None:  # FS2_BENCH_MAIN_PRIORITY=high (measurement aid): the main chain on a high-priority stream
@@ -278,9 +319,10 @@ class Rig:
         torch.cuda.synchronize()
         return n
 
-    def refine(self, log=None, world=1, top=16, candidates=2):
+    def refine(self, log=None, world=1, top=16, candidates=2, deadline=None):
         """Second tuner stage (``hip.refine_tiles_in_step``): the runner-up tiles of the heaviest GEMM shapes tried inside
-        the replayed step.  With several ranks every decision is taken on the maximum over ranks of the timed step."""
+        the replayed step, none after ``deadline`` (``time.perf_counter()``).  With several ranks every decision is taken
+        on the maximum over ranks of the timed step."""
         from fastspeech2_lightning_amd import hip as H
         from fastspeech2_lightning_amd import plan as PL
         if not (H.GEMM_TUNE and PL.ENABLED):
@@ -303,7 +345,7 @@ class Rig:
                 return float(t)
         return H.refine_tiles_in_step(self.step, rounds=8, log=log, settle=self.settle, count_step=eager_step, agree=agree,
                                       top=int(os.environ.get("FS2_REFINE_TOP", top)),
-                                      candidates=int(os.environ.get("FS2_REFINE_CANDIDATES", candidates)))
+                                      candidates=int(os.environ.get("FS2_REFINE_CANDIDATES", candidates)), deadline=deadline)
 
     def plan_info(self):
         plans = self.model.plans
@@ -382,6 +424,45 @@ def gemm_profile(rig, record=True):
     torch.cuda.synchronize()
     ov = sorted(a.elapsed_time(b) for a, b in pairs)[len(pairs) // 2]  # median, ms
     return prof, ov
+
+
+def collect_outputs(model) -> dict:
+    """What the last step handed its caller, as float32 host arrays: every loss term, every floating-point tensor of the
+    forward's output dict, and the updated parameters and the gradient the optimizer step consumed (the model's state
+    dict and gradient state dict -- the reference's layouts -- flattened in their order).  Concatenated on the device: host
+    tensor ops run on torch's intra-op pool, which ``apply_host_budget`` may have sized past the CPUs the process gets."""
+    import numpy as np
+
+    def flat(sd):
+        return torch.cat([t.detach().reshape(-1).float() for t in sd.values() if t.is_floating_point()]).cpu().numpy()
+    out = {f"loss_{k}": np.float32(v) for k, v in model.losses_to_host().items()}
+    for k, v in model.last_output.items():
+        if torch.is_tensor(v) and v.is_floating_point():
+            out[k] = v.detach().float().cpu().numpy()
+    out["parameters"] = flat(model.state_dict())
+    out["gradient"] = flat(model.store.grad_state_dict())
+    return out
+
+
+def write_outputs(arrays: dict, out_dir) -> int:
+    """DIR/<name>.npy for every array, float32.  An array larger than the per-array cap -- the largest power of two that
+    keeps the whole set within DUMP_BUDGET_BYTES, at most 2^21 elements -- is written as a fixed sample of its flattened
+    elements (sorted indices drawn with seed 0 from its size alone, so that every run and every build picks the same
+    ones).  Returns the bytes written."""
+    import numpy as np
+    cap = 1 << 21
+    while sum(4 * min(np.size(a), cap) for a in arrays.values()) > DUMP_BUDGET_BYTES:
+        cap //= 2
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(out / f"{name}.npy", a)
+        total += a.nbytes
+    return total
 
 
 def gemm_numbers(prof, ov):
@@ -591,7 +672,9 @@ def main():
     # (with several ranks only on request: every rank must take the same trials and decisions -- rig.refine agrees on the
     # maximum over ranks and share_tile_table ships rank 0's candidate lists -- but that path has never met real RCCL ranks)
     if (args.refine or world == 1) and not args.no_refine and not use_graph:
-        t_ref, n_ref = rig.refine(log, world, top=32, candidates=3)  # (the headline: ~45 s; the legs take 16 x 2)
+        # (the headline: ~45 s in all, the legs take 16 x 2; a plain run stops trying tiles PLAIN_TUNING_UNTIL_S after start)
+        deadline = None if args.full else T_START + PLAIN_TUNING_UNTIL_S
+        t_ref, n_ref = rig.refine(log, world, top=32, candidates=3, deadline=deadline)
         log(f"in-step tile refinement: {n_ref} signatures changed, {t_ref:.2f} ms/step")
         if os.environ.get("FS2_BENCH_SAVE_TILES"):  # the refined table, for FS2_GEMM_TILE_CACHE of a training run
             H.save_tile_cache(os.environ["FS2_BENCH_SAVE_TILES"])
@@ -607,6 +690,7 @@ def main():
     if graph is None:
         n_settle = rig.settle()
         log(f"launch plan: {rig.plan_info()} after {n_settle} more untimed step(s)")
+    rig.reset_training_state()
 
     if rig.sync is not None:
         rig.wait_events = []
@@ -636,17 +720,20 @@ def main():
         frames_all, padded_all = frames, padded
     losses = {k: float(v) for k, v in model.last_losses.items()}
     plan_info = rig.plan_info()
-    host_own = rig.host_cost() if (graph is None and world == 1) else None
     log(f"timed region: {elapsed / args.steps * 1e3:.2f} ms/step (host enqueue {host_enqueue / args.steps * 1e3:.2f} ms/step)")
+    if args.dump_outputs and rank == 0:
+        n_bytes = write_outputs(collect_outputs(model), args.dump_outputs)
+        log(f"outputs of the last timed step written to {args.dump_outputs} ({n_bytes / 2**20:.1f} MiB)")
+    host_own = rig.host_cost() if (args.full and graph is None and world == 1) else None
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         prof, ov = gemm_profile(rig, record=rank == 0)
         if rank == 0:
             if os.environ.get("FS2_BENCH_GEMM_BREAKDOWN"):
                 log_gemm_breakdown(prof)
             roofline = roofline_of(args, args.precision, prof, ov)
-    log("roofline pass done")
+        log("roofline pass done")
 
     # The other configurations, beside the headline and never as it (`value` above is the exact fp32 MFMA path):
     #  * 32-split: fp32-accurate GEMMs on the bf16 matrix pipe (tests/test_gemm_split_gpu.py), same model and batch;
@@ -654,7 +741,8 @@ def main():
     #  * learn_alignment: the reference's default model (fs2/config/__init__.py:139-142).
     split = bf16_b64 = align = gst_leg = None
     default_cfg = config_signature(args) == {"precision": "32-true", "batch": 32, "gst": False, "learn_alignment": False}
-    if default_cfg and world == 1 and not args.no_extra_legs and graph is None:
+    extra_legs = args.full and default_cfg and world == 1 and not args.no_extra_legs and graph is None
+    if extra_legs:
         n_leg = max(20, args.steps // 4)
         model.precision = "32-split"
         for _ in range(2):
@@ -670,9 +758,10 @@ def main():
                          "normalisations, losses and the optimizer unchanged"}
         log(f"32-split: {dt * 1e3:.2f} ms/step")
     cpu = None
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    want_cpu = args.full and not args.no_cpu_baseline and rank == 0 and world == 1
+    if want_cpu:
         cpu_cfg, cpu_batch = rig.config, rig.batch
-    if default_cfg and world == 1 and not args.no_extra_legs and graph is None:
+    if extra_legs:
         del rig, model, step, run
         torch.cuda.empty_cache()
         rf = not args.no_refine
@@ -681,7 +770,7 @@ def main():
         # BASELINE.json configs[4] at its per-GPU share: GST reference encoder + 16 speakers, mel up to ~1 250 frames,
         # bf16-mixed, batch 64 (fs2/gst/model.py:87-100, fs2/model.py:196-213)
         gst_leg = extra_leg("gst_bf16_b64", "bf16-mixed", 64, False, n_leg, local, not args.no_roofline, gst=True, refine=rf)
-    if not args.no_cpu_baseline and rank == 0 and world == 1:
+    if want_cpu:
         cpu = cpu_baseline(cpu_cfg, cpu_batch)
         log("cpu baseline done")
 

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import time
 from pathlib import Path
 from typing import Optional
 
@@ -390,7 +391,7 @@ _TILE_CALLS = {}
 
 
 def refine_tiles_in_step(step, rounds: int = 5, candidates: int = 2, top: int = 16, min_gain: float = 0.004,
-                         log=None, settle=None, count_step=None, agree=None, timer=None):
+                         log=None, settle=None, count_step=None, agree=None, timer=None, deadline=None):
     """Second tuning stage, run once after warm-up: the per-shape tuner times a GEMM alone, back to back, with its
     operands warm in the Infinity Cache; inside the step the same launch sees cold outputs and a second stream.  For
     the ``top`` signatures by time the next-best isolated tiles are therefore tried IN the step (``step()`` = one whole
@@ -401,7 +402,14 @@ def refine_tiles_in_step(step, rounds: int = 5, candidates: int = 2, top: int = 
     every rank must try the same tiles in the same order and take the same decisions (each trial runs collectives):
     ``agree(ms)`` returns the value all ranks decide on (the maximum over ranks), and the candidate lists must be rank 0's
     (``parallel.share_tile_table`` ships them with the tile table).  ``timer(step, rounds) -> ms per step`` replaces the
-    HIP-event clock (tests)."""
+    HIP-event clock (tests).  ``deadline``: a ``time.perf_counter()`` value after which no further tile is tried (the
+    signatures are tried heaviest first, so a cut drops the smallest prospects; with ``agree`` the ranks stop together)."""
+    def out_of_time():
+        if deadline is None:
+            return False
+        late = float(time.perf_counter() > deadline)
+        return (agree(late) if agree is not None else late) > 0
+
     def event_timer(fn, n):
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -426,8 +434,12 @@ def refine_tiles_in_step(step, rounds: int = 5, candidates: int = 2, top: int = 
                    key=lambda k: -_TILE_TIMINGS[k][0][0] * _TILE_CALLS[k][0])[:top]
     changed = 0
     for key in order:
+        if out_of_time():
+            break
         keep = _TILE_CACHE[key]
         for ms_iso, tile in _TILE_TIMINGS[key][1:1 + candidates]:
+            if out_of_time():
+                break
             _TILE_CACHE[key] = tile
             TILE_GEN[0] += 1
             t = min(timed(), timed())

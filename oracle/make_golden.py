@@ -361,6 +361,41 @@ def dump_ckpt(out_dir: Path):
     print(f"ckpt: losses {losses} then {l4[0]:.6f}; {len(ckpt['optimizer_states'][0]['state'])} parameters with state")
 
 
+def dump_resume(out_dir: Path):
+    """The reference RESUMING A CHECKPOINT WRITTEN BY THE HIP MODEL (``hip_written.ckpt``, from
+    ``python -m tests.test_ckpt_interchange_gpu`` on the GPU): its own ``on_load_checkpoint``, strict ``load_state_dict``,
+    ``torch.optim.AdamW.load_state_dict`` and ``NoamLR.load_state_dict`` in the order Lightning calls them, then one
+    training step.  Recorded: what the reference read from the file, the step's loss and the weights after it, and the
+    checkpoint's hash (the record belongs to that file only)."""
+    import hashlib
+
+    from fs2.model import FastSpeech2 as RefFastSpeech2
+
+    path = out_dir / "hip_written.ckpt"
+    ckpt = torch.load(path, map_location="cpu", weights_only=False)
+    hp = ckpt["hyper_parameters"]
+    ref = RefFastSpeech2(hp["config"], stats=hp["stats"], lang2id=hp["lang2id"], speaker2id=hp["speaker2id"])
+    ref.on_load_checkpoint(ckpt)   # fs2/model.py:353-367: version / model-type checks + config and stats from the file
+    ref.load_state_dict(ckpt["state_dict"], strict=True)
+    (opt,), (sched,) = ref.configure_optimizers()
+    opt.load_state_dict(ckpt["optimizer_states"][0])
+    sched["scheduler"].load_state_dict(ckpt["lr_schedulers"][0])
+    last_epoch = int(sched["scheduler"].last_epoch)
+    g = np.load(out_dir / "ckpt_interchange.npz")
+    batch = {k[6:]: (int(g[k]) if g[k].ndim == 0 else torch.from_numpy(g[k])) for k in g.files if k.startswith("batch/")}
+    ref.train()
+    _, _, l4 = reference_train_steps(ref, batch, 1, opt, sched["scheduler"])
+    save = {"ckpt_sha256": np.asarray(hashlib.sha256(path.read_bytes()).hexdigest()), "loss_4": np.asarray(l4[0]),
+            "use_postnet": np.asarray(bool(ref.config.model.use_postnet)),
+            "warmup_steps": np.asarray(int(ref.config.training.optimizer.warmup_steps)),
+            "last_epoch": np.asarray(last_epoch), "global_step": np.asarray(int(ckpt["global_step"]))}
+    for k, v in ref.state_dict().items():
+        if v.dtype.is_floating_point:
+            save[f"sd_after_4/{k}"] = _np(v)
+    np.savez_compressed(out_dir / "hip_written_ref_resume.npz", **save)
+    print(f"resume: the reference's fourth step from hip_written.ckpt: loss {l4[0]:.6f}")
+
+
 def main():
     out_dir = REPO / "tests" / "golden"
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -371,6 +406,8 @@ def main():
         dump_data(out_dir)
     if len(sys.argv) <= 1 or "ckpt" in sys.argv[1:]:
         dump_ckpt(out_dir)
+    if (len(sys.argv) <= 1 or "resume" in sys.argv[1:]) and (out_dir / "hip_written.ckpt").exists():
+        dump_resume(out_dir)
     only = set(sys.argv[1:])
     for name in C.CASES:
         if only and name not in only:

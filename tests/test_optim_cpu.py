@@ -119,6 +119,14 @@ def test_in_step_tile_refinement_keeps_only_measured_gains():
         # and once more at the end
         assert calls["count"] == 1 and calls["agree"] == 8 and calls["settle"] == 9
         assert H.TILE_GEN[0] > gen0
+        # past its deadline (bench.py's plain run): the baseline is timed, no tile is tried, the ranks agree to stop
+        H._TILE_CACHE[a] = 13
+        calls.update(settle=0, count=0, agree=0)
+        base, changed = H.refine_tiles_in_step(lambda: None, rounds=4, candidates=2, top=8, min_gain=0.004, log=logs.append,
+                                               settle=settle, count_step=count_step, agree=agree,
+                                               timer=lambda fn, n: true_ms(), deadline=0.0)
+        assert changed == 0 and H._TILE_CACHE == {a: 13, b: 7, c: 7} and abs(base - 18.51) < 1e-9 and len(logs) == 1
+        assert calls["count"] == 1 and calls["agree"] == 3 and calls["settle"] == 3
     finally:
         H._TILE_CACHE.clear(); H._TILE_CACHE.update(saved[0])
         H._TILE_TIMINGS.clear(); H._TILE_TIMINGS.update(saved[1])

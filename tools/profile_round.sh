@@ -10,7 +10,7 @@ O=gpurun_out
 # saved here and REPLAYED by the traced / counter runs below (--no-refine + FS2_GEMM_TILE_CACHE), so the profiles are of
 # the configuration the bench line measured -- and no refinement runs under the profiler
 rm -f $O/${TAG}_tiles.json
-FS2_BENCH_SAVE_TILES=$O/${TAG}_tiles.json FS2_BENCH_GEMM_BREAKDOWN=1 python3 bench.py "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
+FS2_BENCH_SAVE_TILES=$O/${TAG}_tiles.json FS2_BENCH_GEMM_BREAKDOWN=1 python3 bench.py --full "$@" > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err || { tail -5 $O/${TAG}_bench.err; exit 1; }
 [ -f $O/${TAG}_tiles.json ] && export FS2_GEMM_TILE_CACHE=$O/${TAG}_tiles.json
 # per-shape GEMM table of the roofline pass (HIP-event intervals, one stream): the first table is the headline configuration's,
 # a second one (default command only) the bf16_mixed_b64 leg's
