@@ -123,6 +123,22 @@ __device__ __forceinline__ void fetch_rows(RowRegs<HD>& regs, const float* __res
                      : make_float4(0, 0, 0, 0);
   }
 }
+// HD 256 (one workgroup per CU, 512 VGPR + AGPR per lane): the backward kernels' owned rows and accumulators leave no
+// room for a tile in flight, so they copy each tile global -> LDS between the two barriers instead (no scratch)
+template <int HD>
+constexpr bool kPrefetch = HD <= 128;
+template <int HD>
+__device__ __forceinline__ void copy_rows(float* __restrict__ dst, const float* __restrict__ src, int ld, int col, int row0,
+                                          int nrows, int tid) {
+  constexpr int LDT = HD + 4, F4 = HD / 4;
+  static_assert(64 * F4 % 256 == 0, "whole passes of the workgroup");
+#pragma unroll 4
+  for (int idx = tid; idx < 64 * F4; idx += 256) {
+    const int r = idx / F4, c4 = idx % F4, row = row0 + r;
+    *reinterpret_cast<float4*>(dst + r * LDT + c4 * 4) =
+        row < nrows ? *reinterpret_cast<const float4*>(src + (long long)row * ld + col + c4 * 4) : make_float4(0, 0, 0, 0);
+  }
+}
 template <int HD>
 __device__ __forceinline__ void commit_rows(float* __restrict__ dst, const RowRegs<HD>& regs, int tid) {
   constexpr int LDT = HD + 4, F4 = HD / 4;
@@ -213,7 +229,7 @@ __device__ __forceinline__ f32x4 acc_pair(const float* __restrict__ tile, int kp
 }
 
 template <int HD, bool BF>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnP p, float* __restrict__ o, float* __restrict__ lse) {
+__global__ __launch_bounds__(256, HD > 128 ? 1 : 2) void attn_fwd_kernel(AttnP p, float* __restrict__ o, float* __restrict__ lse) {
   constexpr int LDT = HD + 4, NJ = HD / 16;
   __shared__ __attribute__((aligned(16))) float Ks[64 * LDT];
   __shared__ __attribute__((aligned(16))) float Vs[64 * LDT];
@@ -317,7 +333,7 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const float* __restrict
 
 // dQ: same walk as the forward (own = queries, tiles = keys)
 template <int HD, bool BF>
-__global__ __launch_bounds__(256, BF ? 2 : 1) void attn_bwd_dq_kernel(AttnP p, const float* __restrict__ dout,
+__global__ __launch_bounds__(256, BF && HD <= 128 ? 2 : 1) void attn_bwd_dq_kernel(AttnP p, const float* __restrict__ dout,
                                                            const float* __restrict__ lse, const float* __restrict__ delta,
                                                            float* __restrict__ dqkv) {
   constexpr int LDT = HD + 4, NJ = HD / 16;
@@ -347,14 +363,21 @@ __global__ __launch_bounds__(256, BF ? 2 : 1) void attn_bwd_dq_kernel(AttnP p, c
   const int kend = min(T, len);
   const unsigned long long rowidx = ((unsigned long long)(b * p.H + h) * T + q) * (unsigned long long)(T + (T & 1));
   RowRegs<HD> kreg, vreg;
-  fetch_rows<HD>(kreg, base, ld, D + h * HD, 0, T, tid);
-  fetch_rows<HD>(vreg, base, ld, 2 * D + h * HD, 0, T, tid);
+  if constexpr (kPrefetch<HD>) {
+    fetch_rows<HD>(kreg, base, ld, D + h * HD, 0, T, tid);
+    fetch_rows<HD>(vreg, base, ld, 2 * D + h * HD, 0, T, tid);
+  }
   for (int key0 = 0; key0 < kend; key0 += 64) {
     __syncthreads();
-    commit_rows<HD>(Ks, kreg, tid);
-    commit_rows<HD>(Vs, vreg, tid);
+    if constexpr (kPrefetch<HD>) {
+      commit_rows<HD>(Ks, kreg, tid);
+      commit_rows<HD>(Vs, vreg, tid);
+    } else {
+      copy_rows<HD>(Ks, base, ld, D + h * HD, key0, T, tid);
+      copy_rows<HD>(Vs, base, ld, 2 * D + h * HD, key0, T, tid);
+    }
     __syncthreads();
-    if (key0 + 64 < kend) {
+    if (kPrefetch<HD> && key0 + 64 < kend) {
       fetch_rows<HD>(kreg, base, ld, D + h * HD, key0 + 64, T, tid);
       fetch_rows<HD>(vreg, base, ld, 2 * D + h * HD, key0 + 64, T, tid);
     }
@@ -433,19 +456,26 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnP p, const float*
   const bool key_ok = key < len;
   const unsigned long long headidx = (unsigned long long)(b * p.H + h) * T;
   RowRegs<HD> qreg, oreg;
-  fetch_rows<HD>(qreg, base, ld, h * HD, 0, T, tid);
-  fetch_rows<HD>(oreg, dout + (long long)b * T * D, D, h * HD, 0, T, tid);
+  if constexpr (kPrefetch<HD>) {
+    fetch_rows<HD>(qreg, base, ld, h * HD, 0, T, tid);
+    fetch_rows<HD>(oreg, dout + (long long)b * T * D, D, h * HD, 0, T, tid);
+  }
   for (int q0 = 0; q0 < T; q0 += 64) {
     __syncthreads();
-    commit_rows<HD>(Qs, qreg, tid);
-    commit_rows<HD>(Os, oreg, tid);
+    if constexpr (kPrefetch<HD>) {
+      commit_rows<HD>(Qs, qreg, tid);
+      commit_rows<HD>(Os, oreg, tid);
+    } else {
+      copy_rows<HD>(Qs, base, ld, h * HD, q0, T, tid);
+      copy_rows<HD>(Os, dout + (long long)b * T * D, D, h * HD, q0, T, tid);
+    }
     if (tid < 64) {
       int qq = q0 + tid;
       lse_s[tid] = qq < T ? lse[((long long)b * p.H + h) * T + qq] : INFINITY;
       delta_s[tid] = qq < T ? delta[((long long)b * p.H + h) * T + qq] : 0.f;
     }
     __syncthreads();
-    if (q0 + 64 < T) {
+    if (kPrefetch<HD> && q0 + 64 < T) {
       fetch_rows<HD>(qreg, base, ld, h * HD, q0 + 64, T, tid);
       fetch_rows<HD>(oreg, dout + (long long)b * T * D, D, h * HD, q0 + 64, T, tid);
     }
@@ -493,6 +523,41 @@ bool attn_args_ok(const void* qkv, int B, int T, int H, int HD) {
   return true;
 }
 
+// measurement aid: first-generation kernels everywhere
+bool gen1_only() {
+  static const bool v = getenv("FS2_ATTN_GEN1") != nullptr;
+  return v;
+}
+
+// Zero-padded heads: [rows][groups*HD] -> [rows][groups*HDp], columns HD..HDp-1 of every group written as zeros (one float4
+// of dst per thread; HDp is a multiple of 16, so a float4 never straddles two groups).
+__global__ __launch_bounds__(256) void attn_pad_heads_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                             long long n4, int groups, int HD, int HDp) {
+  const long long i4 = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i4 >= n4) return;
+  const int w4 = groups * HDp / 4;
+  const long long row = i4 / w4;
+  const int col = (int)(i4 % w4) * 4, grp = col / HDp, d = col % HDp;
+  const float* s = src + row * groups * HD + (long long)grp * HD + d;
+  float4 v;
+  v.x = d < HD ? s[0] : 0.f;
+  v.y = d + 1 < HD ? s[1] : 0.f;
+  v.z = d + 2 < HD ? s[2] : 0.f;
+  v.w = d + 3 < HD ? s[3] : 0.f;
+  reinterpret_cast<float4*>(dst)[i4] = v;
+}
+
+// ... and back: [rows][groups*HDp] -> [rows][groups*HD] (one float of dst per thread: HD may be odd)
+__global__ __launch_bounds__(256) void attn_unpad_heads_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                               long long n, int groups, int HDp, int HD) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int w = groups * HD;
+  const long long row = i / w;
+  const int col = (int)(i % w), grp = col / HD, d = col % HD;
+  dst[i] = src[row * groups * HDp + (long long)grp * HDp + d];
+}
+
 }  // namespace
 
 #define ATTN_DISPATCH_HD(HD_, CALL)                     \
@@ -500,27 +565,76 @@ bool attn_args_ok(const void* qkv, int B, int T, int H, int HD) {
     case 16: { constexpr int HDc = 16; CALL; } break;   \
     case 32: { constexpr int HDc = 32; CALL; } break;   \
     case 64: { constexpr int HDc = 64; CALL; } break;   \
-    default: { constexpr int HDc = 128; CALL; } break;  \
+    case 128: { constexpr int HDc = 128; CALL; } break; \
+    default: { constexpr int HDc = 256; CALL; } break;  \
   }
 #define ATTN_DISPATCH(HD_, BF_, CALL)                              \
   if (BF_) { constexpr bool BFc = true; ATTN_DISPATCH_HD(HD_, CALL) } \
   else { constexpr bool BFc = false; ATTN_DISPATCH_HD(HD_, CALL) }
 
+// The launchers behind the entry points.  HDk: the head width the tensors are laid out in and the kernels run at (16, 32,
+// 64, 128 or 256); scale: 1/sqrt(true head dimension) -- 1/sqrt(HDk) except on the zero-padded route.
+namespace {
+
+int attn_fwd_run(const float* qkv, const int* lens, float* o, float* lse, int B, int T, int H, int HDk, float scale,
+                 Fs2Drop drop, int operand_bf16, hipStream_t s) {
+  if (!gen1_only() && fs2_attn2_supported(HDk, operand_bf16)) {
+    Attn2Args a2{qkv, lens, B, T, H, HDk, scale, drop, operand_bf16 == 2 ? 3 : operand_bf16, nullptr};
+    return fs2_attn2_fwd(a2, o, lse, s);
+  }
+  AttnP p{qkv, lens, B, T, H, scale, drop};
+  dim3 grid((T + 63) / 64, H, B);
+  ATTN_DISPATCH(HDk, operand_bf16 == 1, (attn_fwd_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, o, lse)));
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+int attn_fwd_s_run(const float* qkv, const int* lens, float* o, float* lse, float* scores, long long score_floats, int B,
+                   int T, int H, int HDk, float scale, Fs2Drop drop, int operand_bf16, hipStream_t s) {
+  if (gen1_only() || (HDk != 64 && HDk != 128)) return FS2HIP_EINVAL;
+  if (score_floats < (long long)B * H * T * ((T + 31) & ~31)) return FS2HIP_EINVAL;
+  Attn2Args a2{qkv, lens, B, T, H, HDk, scale, drop, operand_bf16 == 2 ? 3 : 0, nullptr};
+  return fs2_attn2_fwd(a2, o, lse, s, scores);
+}
+
+int attn_bwd_run(const float* qkv, const int* lens, const float* o, const float* dout, const float* lse, float* delta,
+                 float* dqkv, int B, int T, int H, int HDk, float scale, Fs2Drop drop, int operand_bf16, hipStream_t s) {
+  if (!gen1_only() && fs2_attn2_supported(HDk, operand_bf16)) {
+    Attn2Args a2{qkv, lens, B, T, H, HDk, scale, drop, operand_bf16 == 2 ? 3 : operand_bf16, nullptr};
+    return fs2_attn2_bwd(a2, o, dout, lse, delta, dqkv, s);
+  }
+  attn_delta_kernel<<<dim3((B * T + 3) / 4), dim3(256), 0, s>>>(dout, o, delta, B, T, H, HDk);
+  FS2_LAUNCH_CHECK();
+  AttnP p{qkv, lens, B, T, H, scale, drop};
+  dim3 grid((T + 63) / 64, H, B);
+  ATTN_DISPATCH(HDk, operand_bf16 == 1, (attn_bwd_dq_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, dout, lse, delta, dqkv)));
+  FS2_LAUNCH_CHECK();
+  ATTN_DISPATCH(HDk, operand_bf16 == 1, (attn_bwd_dkv_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, dout, lse, delta, dqkv)));
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+// scores: null (the dK/dV kernel recomputes K.Q^T) or fs2hip_attention_fwd_s's
+int attn_bwd_spill_run(const float* qkv, const int* lens, const float* o, const float* dout, const float* lse,
+                       const float* scores, float* aux, float* ds, long long ds_floats, float* dqkv, int B, int T, int H,
+                       int HDk, float scale, Fs2Drop drop, hipStream_t s) {
+  if (!fs2hip_attention_bwd_spill_supported(HDk)) return FS2HIP_EINVAL;
+  Attn2Args a2{qkv, lens, B, T, H, HDk, scale, drop, 0, nullptr};
+  const long long need = fs2_attn2_bwd_spill_elems(a2);
+  if (need == 0 || ds_floats < need) return FS2HIP_EINVAL;
+  return fs2_attn2_bwd_spill(a2, o, dout, lse, aux, ds, dqkv, s, scores);
+}
+
+bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+}  // namespace
+
 extern "C" int fs2hip_attention_fwd(const float* qkv, const int* lens, float* o, float* lse, int B, int T, int H,
                                     int HD, float drop_p, unsigned long long drop_seed,
                                     const unsigned long long* drop_step, int operand_bf16, void* stream) {
   if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16)) return FS2HIP_EINVAL;
-  static const bool old_only = getenv("FS2_ATTN_GEN1") != nullptr;  // measurement aid: first-generation kernels everywhere
-  if (!old_only && fs2_attn2_supported(HD, operand_bf16)) {
-    Attn2Args a2{qkv, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step),
-                 operand_bf16 == 2 ? 3 : operand_bf16, nullptr};
-    return fs2_attn2_fwd(a2, o, lse, (hipStream_t)stream);
-  }
-  AttnP p{qkv, lens, B, T, H, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step)};
-  dim3 grid((T + 63) / 64, H, B);
-  ATTN_DISPATCH(HD, operand_bf16 == 1, (attn_fwd_kernel<HDc, BFc><<<grid, dim3(256), 0, (hipStream_t)stream>>>(p, o, lse)));
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return attn_fwd_run(qkv, lens, o, lse, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step),
+                      operand_bf16, (hipStream_t)stream);
 }
 
 // The forward pass that also writes the masked scores out (operand_bf16 0: fp32 MFMA path, 2: "32-split"; head dims 64 / 128) for
@@ -531,22 +645,12 @@ extern "C" int fs2hip_attention_fwd_s(const float* qkv, const int* lens, float* 
                                       void* stream) {
   if (operand_bf16 != 0 && operand_bf16 != 2) return FS2HIP_EINVAL;  // exact fp32 or three exact bf16 planes
   if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)scores % 16) || !scores) return FS2HIP_EINVAL;
-  static const bool old_only = getenv("FS2_ATTN_GEN1") != nullptr;
-  if (old_only || (HD != 64 && HD != 128)) return FS2HIP_EINVAL;
-  if (score_floats < (long long)B * H * T * ((T + 31) & ~31)) return FS2HIP_EINVAL;
-  Attn2Args a2{qkv, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step),
-               operand_bf16 == 2 ? 3 : 0, nullptr};
-  return fs2_attn2_fwd(a2, o, lse, (hipStream_t)stream, scores);
+  return attn_fwd_s_run(qkv, lens, o, lse, scores, score_floats, B, T, H, HD, 1.f / sqrtf((float)HD),
+                        fs2_make_drop(drop_p, drop_seed, drop_step), operand_bf16, (hipStream_t)stream);
 }
 
-extern "C" int fs2hip_attention_bwd_spill_s(const float* qkv, const int* lens, const float* o, const float* dout,
-                                            const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
-                                            float* dqkv, int B, int T, int H, int HD, float drop_p,
-                                            unsigned long long drop_seed, const unsigned long long* drop_step, void* stream);
-
 extern "C" int fs2hip_attention_bwd_spill_supported(int HD) {
-  static const bool old_only = getenv("FS2_ATTN_GEN1") != nullptr;
-  return (!old_only && (HD == 64 || HD == 128)) ? 1 : 0;
+  return (!gen1_only() && (HD == 64 || HD == 128)) ? 1 : 0;
 }
 
 extern "C" int fs2hip_attention_bwd_spill(const float* qkv, const int* lens, const float* o, const float* dout,
@@ -554,12 +658,10 @@ extern "C" int fs2hip_attention_bwd_spill(const float* qkv, const int* lens, con
                                           int T, int H, int HD, float drop_p, unsigned long long drop_seed,
                                           const unsigned long long* drop_step, void* stream) {
   if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) ||
-      ((uintptr_t)ds % 16) || !fs2hip_attention_bwd_spill_supported(HD))
+      ((uintptr_t)ds % 16))
     return FS2HIP_EINVAL;
-  Attn2Args a2{qkv, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step), 0, nullptr};
-  const long long need = fs2_attn2_bwd_spill_elems(a2);
-  if (need == 0 || ds_floats < need) return FS2HIP_EINVAL;
-  return fs2_attn2_bwd_spill(a2, o, dout, lse, aux, ds, dqkv, (hipStream_t)stream);
+  return attn_bwd_spill_run(qkv, lens, o, dout, lse, nullptr, aux, ds, ds_floats, dqkv, B, T, H, HD, 1.f / sqrtf((float)HD),
+                            fs2_make_drop(drop_p, drop_seed, drop_step), (hipStream_t)stream);
 }
 
 extern "C" int fs2hip_attention_bwd(const float* qkv, const int* lens, const float* o, const float* dout,
@@ -568,22 +670,8 @@ extern "C" int fs2hip_attention_bwd(const float* qkv, const int* lens, const flo
                                     const unsigned long long* drop_step, int operand_bf16, void* stream) {
   if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16))
     return FS2HIP_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  static const bool old_only = getenv("FS2_ATTN_GEN1") != nullptr;
-  if (!old_only && fs2_attn2_supported(HD, operand_bf16)) {
-    Attn2Args a2{qkv, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step),
-                 operand_bf16 == 2 ? 3 : operand_bf16, nullptr};
-    return fs2_attn2_bwd(a2, o, dout, lse, delta, dqkv, s);
-  }
-  attn_delta_kernel<<<dim3((B * T + 3) / 4), dim3(256), 0, s>>>(dout, o, delta, B, T, H, HD);
-  FS2_LAUNCH_CHECK();
-  AttnP p{qkv, lens, B, T, H, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step)};
-  dim3 grid((T + 63) / 64, H, B);
-  ATTN_DISPATCH(HD, operand_bf16 == 1, (attn_bwd_dq_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, dout, lse, delta, dqkv)));
-  FS2_LAUNCH_CHECK();
-  ATTN_DISPATCH(HD, operand_bf16 == 1, (attn_bwd_dkv_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, dout, lse, delta, dqkv)));
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return attn_bwd_run(qkv, lens, o, dout, lse, delta, dqkv, B, T, H, HD, 1.f / sqrtf((float)HD),
+                      fs2_make_drop(drop_p, drop_seed, drop_step), operand_bf16, (hipStream_t)stream);
 }
 
 // fs2hip_attention_bwd_spill with the scores of fs2hip_attention_fwd_s: the dK/dV kernel reads them instead of recomputing
@@ -593,10 +681,75 @@ extern "C" int fs2hip_attention_bwd_spill_s(const float* qkv, const int* lens, c
                                             float* dqkv, int B, int T, int H, int HD, float drop_p,
                                             unsigned long long drop_seed, const unsigned long long* drop_step, void* stream) {
   if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) ||
-      ((uintptr_t)ds % 16) || ((uintptr_t)scores % 16) || !scores || !fs2hip_attention_bwd_spill_supported(HD))
+      ((uintptr_t)ds % 16) || ((uintptr_t)scores % 16) || !scores)
     return FS2HIP_EINVAL;
-  Attn2Args a2{qkv, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step), 0, nullptr};
-  const long long need = fs2_attn2_bwd_spill_elems(a2);
-  if (need == 0 || ds_floats < need) return FS2HIP_EINVAL;
-  return fs2_attn2_bwd_spill(a2, o, dout, lse, aux, ds, dqkv, (hipStream_t)stream, scores);
+  return attn_bwd_spill_run(qkv, lens, o, dout, lse, scores, aux, ds, ds_floats, dqkv, B, T, H, HD, 1.f / sqrtf((float)HD),
+                            fs2_make_drop(drop_p, drop_seed, drop_step), (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Any head dimension 1..256: the kernels run at the padded width fs2hip_attention_padded_dim(HD) with the softmax scale of
+// the true one.  Zero columns of Q and K add exact zeros to every score, zero columns of V give zero output columns.
+// ------------------------------------------------------------------------------------------------------------------
+extern "C" int fs2hip_attention_padded_dim(int HD) {
+  if (HD < 1 || HD > 256) return 0;
+  int w = 16;
+  while (w < HD) w *= 2;
+  return w;
+}
+
+extern "C" int fs2hip_attention_pad_heads(const float* src, float* dst, int rows, int groups, int HD, int HDp,
+                                          void* stream) {
+  if (rows <= 0 || groups <= 0 || HD < 1 || HDp < HD || HDp % 16 || !src || !aligned16(dst)) return FS2HIP_EINVAL;
+  const long long n4 = (long long)rows * groups * HDp / 4;
+  attn_pad_heads_kernel<<<dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(src, dst, n4, groups, HD,
+                                                                                                    HDp);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_attention_unpad_heads(const float* src, float* dst, int rows, int groups, int HDp, int HD,
+                                            void* stream) {
+  if (rows <= 0 || groups <= 0 || HD < 1 || HDp < HD || !src || !dst) return FS2HIP_EINVAL;
+  const long long n = (long long)rows * groups * HD;
+  attn_unpad_heads_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(src, dst, n, groups, HDp,
+                                                                                                      HD);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_attention_fwd_hd(const float* qkv, const int* lens, float* o, float* lse, float* scores,
+                                       long long score_floats, int B, int T, int H, int HD, float drop_p,
+                                       unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
+                                       void* stream) {
+  const int HDk = fs2hip_attention_padded_dim(HD);
+  if (HDk == 0 || B <= 0 || T <= 0 || H <= 0 || operand_bf16 < 0 || operand_bf16 > 2 || !aligned16(qkv) || !aligned16(o))
+    return FS2HIP_EINVAL;
+  const float scale = 1.f / sqrtf((float)HD);
+  const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
+  if (scores) {
+    if (operand_bf16 == 1 || !aligned16(scores)) return FS2HIP_EINVAL;
+    return attn_fwd_s_run(qkv, lens, o, lse, scores, score_floats, B, T, H, HDk, scale, drop, operand_bf16,
+                          (hipStream_t)stream);
+  }
+  return attn_fwd_run(qkv, lens, o, lse, B, T, H, HDk, scale, drop, operand_bf16, (hipStream_t)stream);
+}
+
+extern "C" int fs2hip_attention_bwd_hd(const float* qkv, const int* lens, const float* o, const float* dout,
+                                       const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
+                                       float* dqkv, int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
+                                       const unsigned long long* drop_step, int operand_bf16, void* stream) {
+  const int HDk = fs2hip_attention_padded_dim(HD);
+  if (HDk == 0 || B <= 0 || T <= 0 || H <= 0 || operand_bf16 < 0 || operand_bf16 > 2 || !aligned16(qkv) || !aligned16(o) ||
+      !aligned16(dout) || !aligned16(dqkv))
+    return FS2HIP_EINVAL;
+  const float scale = 1.f / sqrtf((float)HD);
+  const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
+  if (ds) {  // the spilled-dS backward: exact fp32 or "32-split", whose dK/dV kernel is the fp32 one
+    if (operand_bf16 == 1 || !aligned16(ds) || !aligned16(scores)) return FS2HIP_EINVAL;
+    return attn_bwd_spill_run(qkv, lens, o, dout, lse, scores, aux, ds, ds_floats, dqkv, B, T, H, HDk, scale, drop,
+                              (hipStream_t)stream);
+  }
+  if (scores) return FS2HIP_EINVAL;
+  return attn_bwd_run(qkv, lens, o, dout, lse, aux, dqkv, B, T, H, HDk, scale, drop, operand_bf16, (hipStream_t)stream);
 }

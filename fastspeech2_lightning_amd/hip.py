@@ -82,6 +82,11 @@ SIGNATURES = {
     "fs2hip_attention_bwd_spill": "pppppppqpiiiifQpp",
     "fs2hip_attention_fwd_s": "pppppqiiiifQpip",
     "fs2hip_attention_bwd_spill_s": "ppppppppqpiiiifQpp",
+    "fs2hip_attention_padded_dim": "i",
+    "fs2hip_attention_pad_heads": "ppiiiip",
+    "fs2hip_attention_unpad_heads": "ppiiiip",
+    "fs2hip_attention_fwd_hd": "pppppqiiiifQpip",
+    "fs2hip_attention_bwd_hd": "ppppppppqpiiiifQpip",
     "fs2hip_attention_fwd_b": "ppppiiiifQpp",
     "fs2hip_attention_bwd_b": "pppppppiiiifQpp",
     "fs2hip_attention_bwd_b_spill": "pppppppqpiiiifQpp",
@@ -1362,19 +1367,55 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dx_add=None, defer=Fa
 ATTN_SCORES = os.environ.get("FS2_ATTN_SCORES", "1") != "0"
 
 
+#: head dims the attention kernels are built for; the others run zero-padded to ``attention_padded_dim``
+ATTN_NATIVE_HD = (16, 32, 64, 128)
+#: the largest head dimension the attention kernels take (padded or not)
+ATTN_MAX_HD = 256
+
+
+def attention_padded_dim(HD: int) -> int:
+    """The head width the kernels run a head dimension at: HD itself for 16 / 32 / 64 / 128 / 256, otherwise the next of
+    those above it (the tensors are zero-padded to it); 0 outside 1..256."""
+    return int(lib().fs2hip_attention_padded_dim(int(HD)))
+
+
 def attention_scores_kept(HD: int) -> bool:
     """True when ``attention_fwd(save_scores=True)`` writes the scores out for ``attention_bwd(scores=...)``: exact fp32 or
-    "32-split", head dims of the second-generation kernels, spilled-dS backward on."""
-    return GEMM_BF16 in (0, 2) and ATTN_SPILL and ATTN_SCORES and bool(lib().fs2hip_attention_bwd_spill_supported(int(HD)))
+    "32-split", head dims (padded) of the second-generation kernels, spilled-dS backward on."""
+    HDp = attention_padded_dim(HD)
+    return (GEMM_BF16 in (0, 2) and ATTN_SPILL and ATTN_SCORES and HDp > 0
+            and bool(lib().fs2hip_attention_bwd_spill_supported(HDp)))
+
+
+def _head_dim(D, H, fn):
+    HD = D // H
+    _req(0 < HD <= ATTN_MAX_HD, f"{fn}: head dimension {HD} is outside 1..{ATTN_MAX_HD}")
+    return HD
+
+
+def _pad_heads(x, rows, groups, HD, HDp):
+    """[rows][groups*HD] -> a fresh [rows][groups*HDp] with zero pad columns (written by the kernel: no fill launch)."""
+    xp = torch.empty(rows, groups * HDp, device=x.device, dtype=torch.float32)
+    _ok(lib().fs2hip_attention_pad_heads(_p(x), _p(xp), rows, groups, HD, HDp, _stream()), "attention_pad_heads")
+    return xp
+
+
+def _unpad_heads(xp, out, rows, groups, HDp, HD):
+    _ok(lib().fs2hip_attention_unpad_heads(_p(xp), _p(out), rows, groups, HDp, HD, _stream()), "attention_unpad_heads")
+    return out
 
 
 def attention_fwd(qkv, lens, B, T, H, drop: Drop = NO_DROP, save_scores=False):
     """``save_scores`` (training forward): returns (o, lse, scores) -- scores [B, H, T, T rounded up to 32] for the backward
-    pass, or None where ``attention_scores_kept`` says no."""
+    pass, or None where ``attention_scores_kept`` says no.  Any head dimension up to 256: 16 / 32 / 64 / 128 run as they
+    are, the others on the zero-padded route (``attention_padded_dim``)."""
     _chk(qkv, name="qkv"); _chk(lens, torch.int32, "lens")
     D = qkv.shape[-1] // 3
     _req(_rows(qkv) == B * T and qkv.shape[-1] == 3 * D and D % H == 0 and lens.numel() == B,
          "attention_fwd: shape mismatch")
+    HD = _head_dim(D, H, "attention_fwd")
+    if HD not in ATTN_NATIVE_HD:
+        return _attention_fwd_hd(qkv, lens, B, T, H, HD, drop, save_scores)
     o = torch.empty(B, T, D, device=qkv.device, dtype=torch.float32)
     lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
     if save_scores:
@@ -1388,6 +1429,22 @@ def attention_fwd(qkv, lens, B, T, H, drop: Drop = NO_DROP, save_scores=False):
     _ok(lib().fs2hip_attention_fwd(_p(qkv), _p(lens), _p(o), _p(lse), B, T, H, D // H, drop.p, drop.seed,
                                    drop.step_ptr, int(GEMM_BF16), _stream()), "attention_fwd")
     return o, lse
+
+
+def _attention_fwd_hd(qkv, lens, B, T, H, HD, drop, save_scores):
+    """The forward pass at a head dimension the kernels are not built for: q | k | v zero-padded to HDp columns per head
+    (skipped at HDp = HD = 256), the kernels at HDp with the softmax scale of HD, o cut back to HD columns per head."""
+    HDp, D, rows = attention_padded_dim(HD), H * HD, B * T
+    qkvp = qkv if HDp == HD else _pad_heads(qkv, rows, 3 * H, HD, HDp)
+    op = torch.empty(B, T, H * HDp, device=qkv.device, dtype=torch.float32)
+    lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
+    sc = None
+    if save_scores and attention_scores_kept(HD):
+        sc = torch.empty(B, H, T, (T + 31) // 32 * 32, device=qkv.device, dtype=torch.float32)
+    _ok(lib().fs2hip_attention_fwd_hd(_p(qkvp), _p(lens), _p(op), _p(lse), _p(sc), 0 if sc is None else sc.numel(), B, T, H,
+                                      HD, drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()), "attention_fwd_hd")
+    o = op if HDp == HD else _unpad_heads(op, torch.empty(B, T, D, device=qkv.device, dtype=torch.float32), rows, H, HDp, HD)
+    return (o, lse, sc) if save_scores else (o, lse)
 
 
 #: FS2_ATTN_SPILL=0: the fp32 attention backward recomputes S and dP in both gradient kernels (the round-2 structure)
@@ -1424,6 +1481,9 @@ def attention_bwd(qkv, lens, o, dout, lse, B, T, H, drop: Drop = NO_DROP, scores
     D = qkv.shape[-1] // 3
     _req(_rows(qkv) == B * T and o.numel() == B * T * D and dout.numel() == B * T * D and lse.numel() == B * H * T
          and lens.numel() == B, "attention_bwd: shape mismatch")
+    HD = _head_dim(D, H, "attention_bwd")
+    if HD not in ATTN_NATIVE_HD:
+        return _attention_bwd_hd(qkv, lens, o, dout, lse, B, T, H, HD, drop, scores)
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(2 * lse.numel() + 4, device=lse.device, dtype=torch.float32)  # scratch: see fs2hip.h
     if GEMM_BF16 in (0, 2) and ATTN_SPILL and lib().fs2hip_attention_bwd_spill_supported(D // H):
@@ -1444,6 +1504,34 @@ def attention_bwd(qkv, lens, o, dout, lse, B, T, H, drop: Drop = NO_DROP, scores
     _ok(lib().fs2hip_attention_bwd(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(delta), _p(dqkv), B, T, H, D // H,
                                    drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()), "attention_bwd")
     return dqkv
+
+
+def _attention_bwd_hd(qkv, lens, o, dout, lse, B, T, H, HD, drop, scores):
+    """The backward pass of ``_attention_fwd_hd``: qkv, o and dout zero-padded to HDp columns per head (o's pad columns
+    are the forward's exact zeros), the kernels at HDp, dqkv cut back to HD columns per head."""
+    HDp, rows = attention_padded_dim(HD), B * T
+    pad = HDp != HD
+    qkvp = _pad_heads(qkv, rows, 3 * H, HD, HDp) if pad else qkv
+    op = _pad_heads(o, rows, H, HD, HDp) if pad else o
+    doutp = _pad_heads(dout, rows, H, HD, HDp) if pad else dout
+    dqkvp = torch.empty(rows, 3 * H * HDp, device=qkv.device, dtype=torch.float32)
+    aux = torch.empty(2 * lse.numel() + 4, device=lse.device, dtype=torch.float32)
+    ds, n = None, 0
+    if GEMM_BF16 in (0, 2) and ATTN_SPILL and lib().fs2hip_attention_bwd_spill_supported(HDp):
+        # (a step allocation, not reserve_scratch: under a launch plan it lives in the plan's own pool)
+        n = B * H * T * ((T + 31) // 32 * 32)
+        ds = torch.empty(n, device=qkv.device, dtype=torch.float32)
+        if scores is not None:
+            _chk(scores, name="scores")
+            _req(scores.numel() == n, "attention_bwd: scores must be [B, H, T, T rounded up to 32]")
+    else:
+        scores = None
+    _ok(lib().fs2hip_attention_bwd_hd(_p(qkvp), _p(lens), _p(op), _p(doutp), _p(lse), _p(scores), _p(aux), _p(ds), n,
+                                      _p(dqkvp), B, T, H, HD, drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()),
+        "attention_bwd_hd")
+    if not pad:
+        return dqkvp.view_as(qkv)
+    return _unpad_heads(dqkvp, torch.empty_like(qkv), rows, 3 * H, HDp, HD)
 
 
 def attention_b_supported(HD: int) -> bool:

@@ -337,13 +337,14 @@ POSTNET_IM2COL = os.environ.get("FS2_POSTNET_IM2COL", "1") != "0"
 class SelfAttention:
     """LayerNorm -> nn.MultiheadAttention(key_padding_mask) -> Dropout; y = x + f(x)."""
 
-    HEAD_DIMS = (16, 32, 64, 128)  # what the attention kernels are built for (fs2hip_attention_fwd refuses the rest)
+    MAX_HEAD_DIM = H.ATTN_MAX_HD  # any integer head dimension up to this (hip.attention_fwd pads the ones it is not built for)
 
     def __init__(self, S, env: Env, prefix, d, heads, p, dims_ok=False):
         self.dims_ok = dims_ok
-        if heads <= 0 or d % heads or d // heads not in self.HEAD_DIMS:
+        if heads <= 0 or d % heads or d // heads > self.MAX_HEAD_DIM:
             raise ValueError(f"Conformer attention: input_dim {d} / heads {heads} gives a head dimension of "
-                             f"{d / max(heads, 1):g}; this build has attention kernels for head dimensions {self.HEAD_DIMS}")
+                             f"{d / max(heads, 1):g}; the attention kernels take integer head dimensions up to "
+                             f"{self.MAX_HEAD_DIM}")
         self.S, self.env, self.p, self.heads = S, env, p, heads
         self.ln = LayerNorm(S, prefix + "self_attn_layer_norm.", d)
         a = prefix + "self_attn."

@@ -222,13 +222,13 @@ int fs2hip_layernorm_bwd_x(const void* dy, const float* x, const float* gamma, c
 
 /* ------------------------------------------------------------------------------------
  * Multi-head self-attention with key-padding mask (flash style; fp32 MFMA: v_mfma_f32_32x32x2_f32 for
- * head dims 64 / 128 -- attention2.hip -- and 16x16x4 for head dims 16 / 32).
+ * head dims 64 / 128 -- attention2.hip -- and 16x16x4 for head dims 16 / 32 / 256).
  * Replaces nn.MultiheadAttention's scaled-dot-product core inside torchaudio's
  * ConformerLayer (call sites fs2/model.py:193, :241).
  *   qkv  [B*T][3*H*HD]  in_proj output (q | k | v);  lens [B] int32 (keys >= lens[b] masked)
  *   o    [B*T][H*HD];   lse [B][H][T] (log-sum-exp per query, saved for the backward)
  *   dropout acts on the normalised probabilities (attention dropout), mask regenerated
- *   from (seed, b, h, q, k) in the backward.  HD in {16, 32, 64, 128}.
+ *   from (seed, b, h, q, k) in the backward.  HD in {16, 32, 64, 128} (other head dims: the _hd entry points below).
  * bwd: delta = scratch of 2*B*H*T + 4 floats ({lse', delta'} pairs per row and head); dqkv [B*T][3*H*HD]
  *      fully written.
  * operand_bf16 = 1 ("bf16-mixed"): the operands of all five products (Q, K, V, dO, P, dS) are rounded to bf16 for
@@ -267,6 +267,29 @@ int fs2hip_attention_bwd_spill_s(const float* qkv, const int* lens, const float*
                                  const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
                                  float* dqkv, int B, int T, int H, int HD, float drop_p,
                                  unsigned long long drop_seed, const unsigned long long* drop_step, void* stream);
+
+/* Any head dimension 1 <= HD <= 256.  The kernels run at the padded width HDp = fs2hip_attention_padded_dim(HD) (the
+ * smallest of 16, 32, 64, 128, 256 that holds HD; 0: refused) with the softmax scale 1/sqrt(HD) of the TRUE head dimension.
+ * fs2hip_attention_pad_heads: [rows][groups*HD] -> [rows][groups*HDp], the pad columns written as zeros (qkv: groups = 3H;
+ *   dout and o: groups = H).  fs2hip_attention_unpad_heads: [rows][groups*HDp] -> [rows][groups*HD] (o, dqkv).
+ * fs2hip_attention_fwd_hd / _bwd_hd: the operations above on the padded tensors (qkv [B*T][3*H*HDp], o / dout
+ *   [B*T][H*HDp], dqkv [B*T][3*H*HDp]; at HD = HDp the unpadded ones).  Zero columns of Q and K add exact zeros to every
+ *   score and zero columns of V give zero output columns, so the results are those of the true head dimension; the
+ *   dropout mask is that of fs2hip_attention_fwd (it depends on b, h, q, key only).
+ *   fwd_hd: scores non-null = fs2hip_attention_fwd_s (operand_bf16 0 or 2, HDp 64 / 128).
+ *   bwd_hd: ds non-null = the spilled-dS backward (fs2hip_attention_bwd_spill, _s when scores is non-null; operand_bf16
+ *   0 or 2, HDp 64 / 128); ds null = fs2hip_attention_bwd with aux as its delta scratch. */
+int fs2hip_attention_padded_dim(int HD);
+int fs2hip_attention_pad_heads(const float* src, float* dst, int rows, int groups, int HD, int HDp, void* stream);
+int fs2hip_attention_unpad_heads(const float* src, float* dst, int rows, int groups, int HDp, int HD, void* stream);
+int fs2hip_attention_fwd_hd(const float* qkv, const int* lens, float* o, float* lse, float* scores,
+                            long long score_floats, int B, int T, int H, int HD, float drop_p,
+                            unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
+                            void* stream);
+int fs2hip_attention_bwd_hd(const float* qkv, const int* lens, const float* o, const float* dout,
+                            const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
+                            float* dqkv, int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
+                            const unsigned long long* drop_step, int operand_bf16, void* stream);
 
 /* The same attention on tensors that ARE bf16 in memory (precision "bf16-mixed" with bf16 activation
  * storage; torch.autocast(bfloat16) around nn.MultiheadAttention, call sites fs2/model.py:193, :241):
