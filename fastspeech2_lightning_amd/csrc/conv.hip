@@ -232,6 +232,21 @@ __device__ __forceinline__ void dw_st8_global(void* dst, long long e, const floa
     *reinterpret_cast<float4*>((float*)dst + e + 4) = b;
   }
 }
+// the same from registers
+template <bool OB>
+__device__ __forceinline__ void dw_st8_global_r(void* dst, long long e, const float (&v)[8]) {
+  if constexpr (OB) {
+    uint4 u;
+    u.x = (unsigned)dw_bf16(v[0]) | ((unsigned)dw_bf16(v[1]) << 16);
+    u.y = (unsigned)dw_bf16(v[2]) | ((unsigned)dw_bf16(v[3]) << 16);
+    u.z = (unsigned)dw_bf16(v[4]) | ((unsigned)dw_bf16(v[5]) << 16);
+    u.w = (unsigned)dw_bf16(v[6]) | ((unsigned)dw_bf16(v[7]) << 16);
+    *reinterpret_cast<uint4*>((unsigned short*)dst + e) = u;
+  } else {
+    *reinterpret_cast<float4*>((float*)dst + e) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>((float*)dst + e + 4) = make_float4(v[4], v[5], v[6], v[7]);
+  }
+}
 
 template <int K, bool STATS, bool XB>
 __global__ __launch_bounds__(256) void dwconv_glu_fwd_tile_kernel(const void* __restrict__ x, int ldx,
@@ -425,6 +440,377 @@ __global__ __launch_bounds__(256) void dwconv_glu_bwd_tile_kernel(const void* __
   }
 }
 
+// ---- any odd width up to KMAX: run-time K ---------------------------------------------------------------------------
+// The kernels above hold the taps and each thread's window in registers sized by K (more than 300 VGPRs in the
+// backward pass at K = 63).  Here the workgroup's window -- (4 RUN + K - 1) rows x 64 channels, fp32 -- sits in LDS, the
+// taps are read from global memory (256 bytes per tap and wavefront, L1-resident), and every thread walks the taps at
+// run time in chunks of KC: per chunk KC taps and a (RUN + KC - 1)-row slice of its window in registers.  The loops
+// over outputs and taps are only interchanged: every output, data gradient and tap gradient takes its terms in the
+// order of the kernels above, so for the six built widths the results are their bits.  The tap gradients are reduced
+// across the four wavefronts one chunk at a time, through KC rows of LDS.  LDS (dynamic, all of it): 256 (4 RUN + K - 1)
+// bytes (+ 2 KB of statistics) forward, twice that backward: at most 63 KB, at K = 63.
+constexpr int KMAX = 63, KC = 16;
+
+__host__ __device__ constexpr int dwg_rows(int K) { return 4 * RUN + K - 1; }
+
+// acc[o] = bias, then acc[o] = fmaf(w[k], a[o + k], acc[o]) for k ascending.  win: the thread's window (row stride 64).
+__device__ __forceinline__ void dwg_conv(const float* win, const float* __restrict__ w, int C, int c, bool cok, int K,
+                                         float bs, float (&acc)[RUN]) {
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) acc[o] = bs;
+  for (int kc = 0; kc < K; kc += KC) {
+    float wk[KC], aw[RUN + KC - 1];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) wk[j] = (cok && kc + j < K) ? w[(kc + j) * C + c] : 0.f;
+#pragma unroll
+    for (int i = 0; i < RUN + KC - 1; ++i) aw[i] = win[min(kc + i, K + RUN - 2) * 64];
+#pragma unroll
+    for (int j = 0; j < KC; ++j)
+      if (kc + j < K) {
+#pragma unroll
+        for (int o = 0; o < RUN; ++o) acc[o] = fmaf(wk[j], aw[o + j], acc[o]);
+      }
+  }
+}
+
+// da[o] = 0, then da[o] = fmaf(w[k], g[o + K - 1 - k], da[o]) for k ascending.  gwin: the thread's window of dy.
+__device__ __forceinline__ void dwg_dgrad(const float* gwin, const float* __restrict__ w, int C, int c, bool cok, int K,
+                                          float (&da)[RUN]) {
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) da[o] = 0.f;
+  for (int kc = 0; kc < K; kc += KC) {
+    const int base = K - KC - kc;  // gw[i] = g[base + i]; rows below 0 are never used
+    float wk[KC], gw[RUN + KC - 1];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) wk[j] = (cok && kc + j < K) ? w[(kc + j) * C + c] : 0.f;
+#pragma unroll
+    for (int i = 0; i < RUN + KC - 1; ++i) gw[i] = gwin[max(base + i, 0) * 64];
+#pragma unroll
+    for (int j = 0; j < KC; ++j)
+      if (kc + j < K) {
+#pragma unroll
+        for (int o = 0; o < RUN; ++o) da[o] = fmaf(wk[j], gw[o + KC - 1 - j], da[o]);
+      }
+  }
+}
+
+// Tap gradients (dw[k]: fmaf(gy[o], a[o + k], .) over o ascending) and dbias (gy summed over o), each summed over the
+// four wavefronts (0 + 1 + 2 + 3, as above) into partial [blk][K + 1][C].  red: 4 KC x 64 floats of LDS that nothing
+// else uses meanwhile; win: the thread's window of a.  Called by the whole workgroup; every read of win is over when
+// it returns.
+__device__ __forceinline__ void dwg_wgrad(const float* win, const float (&gy)[RUN], float* red, float* __restrict__ partial,
+                                          long long blk, int C, int c, bool cok, int K, int lane, int wave) {
+  for (int kc = 0; kc < K; kc += KC) {
+    float aw[RUN + KC - 1];
+#pragma unroll
+    for (int i = 0; i < RUN + KC - 1; ++i) aw[i] = win[min(kc + i, K + RUN - 2) * 64];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      float dwk = 0.f;
+      if (kc + j < K) {
+#pragma unroll
+        for (int o = 0; o < RUN; ++o) dwk = fmaf(gy[o], aw[o + j], dwk);
+      }
+      red[(wave * KC + j) * 64 + lane] = dwk;
+    }
+    __syncthreads();
+    for (int j = wave; j < KC; j += 4)
+      if (cok && kc + j < K)
+        partial[(blk * (K + 1) + kc + j) * C + c] = red[(0 * KC + j) * 64 + lane] + red[(1 * KC + j) * 64 + lane] +
+                                                    red[(2 * KC + j) * 64 + lane] + red[(3 * KC + j) * 64 + lane];
+    __syncthreads();
+  }
+  float db = 0.f;
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) db += gy[o];
+  red[wave * 64 + lane] = db;
+  __syncthreads();
+  if (wave == 0 && cok) partial[(blk * (K + 1) + K) * C + c] = red[lane] + red[64 + lane] + red[128 + lane] + red[192 + lane];
+}
+
+// BatchNorm statistics of the workgroup's four runs -> partial [blk][2][C], as in dwconv_fwd_kernel
+__device__ __forceinline__ void dwg_stats(float (*red)[2][64], float* __restrict__ partial, float s1, float s2,
+                                          float pivot, int T, int tbase, int t0, int C, int c, bool cok, int lane,
+                                          int wave) {
+  const int nw = max(0, min(RUN, T - t0));
+  const float inv = nw > 0 ? 1.f / (float)nw : 0.f;
+  red[wave][0][lane] = pivot + s1 * inv;
+  red[wave][1][lane] = fmaxf(s2 - s1 * s1 * inv, 0.f);
+  __syncthreads();
+  if (wave == 0 && cok) {
+    float n = 0.f, mean = 0.f, m2 = 0.f;  // Chan merge of the four runs
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float nr = (float)max(0, min(RUN, T - (tbase + w * RUN)));
+      if (nr > 0.f) {
+        const float delta = red[w][0][lane] - mean, nt = n + nr;
+        mean += delta * (nr / nt);
+        m2 += red[w][1][lane] + delta * delta * (n * nr / nt);
+        n = nt;
+      }
+    }
+    long long blk = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+    partial[(blk * 2 + 0) * C + c] = mean;
+    partial[(blk * 2 + 1) * C + c] = m2;
+  }
+}
+
+// the workgroup's rows of a = value (* sigmoid(gate)) for this thread's channel: one element per lane and load
+template <bool GLU, bool XB>
+__device__ __forceinline__ void dwg_stage(float* as, const void* __restrict__ x, int ldx, int b, int T, int C, int c,
+                                          bool cok, int tbase, int PAD, int ROWS, int lane, int wave) {
+#pragma unroll 4
+  for (int r = wave; r < ROWS; r += 4) {
+    const int t = tbase - PAD + r;
+    float v = 0.f;
+    if (cok && t >= 0 && t < T) {
+      const long long row = ((long long)b * T + t) * ldx;
+      v = dw_ld<XB>(x, row + c);
+      if (GLU) v *= fs2_sigmoid(dw_ld<XB>(x, row + C + c));
+    }
+    as[r * 64 + lane] = v;
+  }
+}
+
+// per-thread-window form (any C): the variants of dwconv_fwd_kernel
+template <bool GLU, bool STATS, bool XB = false, bool YB = XB>
+__global__ __launch_bounds__(256) void dwconv_fwd_generic_kernel(const void* __restrict__ x, int ldx,
+                                                                  const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, void* __restrict__ y,
+                                                                  float* __restrict__ partial, int B, int T, int C,
+                                                                  int K) {
+  extern __shared__ __attribute__((aligned(16))) float dwg_lds[];  // as [ROWS][64] | red [4][2][64]
+  const int PAD = (K - 1) / 2, ROWS = dwg_rows(K);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const int tbase = blockIdx.y * (4 * RUN), t0 = tbase + wave * RUN;
+  const int b = blockIdx.z;
+  const bool cok = c < C;
+  float* as = dwg_lds;
+  dwg_stage<GLU, XB>(as, x, ldx, b, T, C, c, cok, tbase, PAD, ROWS, lane, wave);
+  const float bs = (cok && bias) ? bias[c] : 0.f;
+  __syncthreads();
+  float acc[RUN];
+  dwg_conv(as + wave * RUN * 64 + lane, w, C, c, cok, K, bs, acc);
+  float s1 = 0.f, s2 = 0.f, pivot = 0.f;
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) {
+    int t = t0 + o;
+    if (cok && t < T) {
+      float v = acc[o];
+      if constexpr (YB) {
+        const unsigned short r = dw_bf16(v);
+        ((unsigned short*)y)[((long long)b * T + t) * C + c] = r;
+        v = __builtin_bit_cast(float, (unsigned)r << 16);
+      } else {
+        ((float*)y)[((long long)b * T + t) * C + c] = v;
+      }
+      if (STATS) {
+        if (o == 0) pivot = v;
+        const float d = v - pivot;
+        s1 += d;
+        s2 += d * d;
+      }
+    }
+  }
+  if (STATS)
+    dwg_stats(reinterpret_cast<float(*)[2][64]>(dwg_lds + ROWS * 64), partial, s1, s2, pivot, T, tbase, t0, C, c, cok,
+              lane, wave);
+}
+
+// the variants of dwconv_bwd_kernel
+template <bool GLU, bool DXB = false, bool XB = false>
+__global__ __launch_bounds__(256) void dwconv_bwd_generic_kernel(const void* __restrict__ dy, const void* __restrict__ x,
+                                                                  int ldx, const float* __restrict__ w,
+                                                                  void* __restrict__ dxv, float* __restrict__ partial,
+                                                                  int B, int T, int C, int K) {
+  extern __shared__ __attribute__((aligned(16))) float dwg_lds[];  // as [ROWS][64] | gs [ROWS][64] (then: red)
+  const int PAD = (K - 1) / 2, ROWS = dwg_rows(K);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = blockIdx.x * 64 + lane;
+  const int tbase = blockIdx.y * (4 * RUN), t0 = tbase + wave * RUN;
+  const int b = blockIdx.z;
+  const bool cok = c < C;
+  float *as = dwg_lds, *gs = dwg_lds + ROWS * 64;
+  dwg_stage<GLU, XB>(as, x, ldx, b, T, C, c, cok, tbase, PAD, ROWS, lane, wave);
+#pragma unroll 4
+  for (int r = wave; r < ROWS; r += 4) {
+    const int t = tbase - PAD + r;
+    gs[r * 64 + lane] = (cok && t >= 0 && t < T) ? dw_ld<XB>(dy, ((long long)b * T + t) * C + c) : 0.f;
+  }
+  __syncthreads();
+  float da[RUN], gy[RUN];
+  dwg_dgrad(gs + wave * RUN * 64 + lane, w, C, c, cok, K, da);
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) gy[o] = gs[(wave * RUN + o + PAD) * 64 + lane];
+  __syncthreads();  // gs becomes the tap-gradient reduction buffer
+  dwg_wgrad(as + wave * RUN * 64 + lane, gy, gs, partial, (long long)b * gridDim.y + blockIdx.y, C, c, cok, K, lane,
+            wave);
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) {
+    int t = t0 + o;
+    if (cok && t < T) {  // value and gate read again (L2), the sigmoid recomputed: the values of dwconv_bwd_kernel
+      const long long xrow = ((long long)b * T + t) * ldx;
+      const float vc = dw_ld<XB>(x, xrow + c), sc = GLU ? fs2_sigmoid(dw_ld<XB>(x, xrow + C + c)) : 0.f;
+      if constexpr (DXB) {
+        unsigned short* row = (unsigned short*)dxv + xrow;
+        if (GLU) {
+          row[c] = dw_bf16(da[o] * sc);
+          row[C + c] = dw_bf16(da[o] * vc * sc * (1.f - sc));
+        } else {
+          row[c] = dw_bf16(da[o]);
+        }
+      } else {
+        float* row = (float*)dxv + xrow;
+        if (GLU) {
+          row[c] = da[o] * sc;
+          row[C + c] = da[o] * vc * sc * (1.f - sc);
+        } else {
+          row[c] = da[o];
+        }
+      }
+    }
+  }
+}
+
+// the workgroup's rows of value * sigmoid(gate) (and of dy, when gs is given): 16 bytes per lane and load
+template <bool XB>
+__device__ __forceinline__ void dwg_stage8(float* as, float* gs, const void* __restrict__ x, const void* __restrict__ dy,
+                                           int ldx, int b, int T, int C, int c0, int tbase, int PAD, int ROWS, int tid) {
+  const int sub = tid & 7;
+  for (int r = tid >> 3; r < ROWS; r += 32) {
+    const int t = tbase - PAD + r;
+    float a8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, d8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (t >= 0 && t < T) {
+      const long long row = ((long long)b * T + t) * ldx + c0 + 8 * sub;
+      float v8[8], g8[8];
+      dw_ld8<XB>(x, row, v8);
+      dw_ld8<XB>(x, row + C, g8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a8[j] = v8[j] * fs2_sigmoid(g8[j]);
+      if (gs) dw_ld8<XB>(dy, ((long long)b * T + t) * C + c0 + 8 * sub, d8);
+    }
+    dw_st8(&as[r * 64 + 8 * sub], a8);
+    if (gs) dw_st8(&gs[r * 64 + 8 * sub], d8);
+  }
+}
+
+// tiled form (C % 64 == 0, ldx % 8 == 0): the variants of dwconv_glu_fwd_tile_kernel
+template <bool STATS, bool XB>
+__global__ __launch_bounds__(256) void dwconv_glu_fwd_tile_generic_kernel(const void* __restrict__ x, int ldx,
+                                                                           const float* __restrict__ w,
+                                                                           const float* __restrict__ bias,
+                                                                           void* __restrict__ y,
+                                                                           float* __restrict__ partial, int B, int T,
+                                                                           int C, int K) {
+  // as [ROWS][64] (then: the results, [4 RUN][64]) | red [4][2][64]
+  extern __shared__ __attribute__((aligned(16))) float dwg_lds[];
+  const int PAD = (K - 1) / 2, ROWS = dwg_rows(K), TT = 4 * RUN;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c0 = blockIdx.x * 64, c = c0 + lane;
+  const int tbase = blockIdx.y * TT, t0 = tbase + wave * RUN;
+  const int b = blockIdx.z;
+  float* as = dwg_lds;
+  dwg_stage8<XB>(as, nullptr, x, nullptr, ldx, b, T, C, c0, tbase, PAD, ROWS, tid);
+  const float bs = bias ? bias[c] : 0.f;
+  __syncthreads();
+  float acc[RUN];
+  dwg_conv(as + wave * RUN * 64 + lane, w, C, c, true, K, bs, acc);
+  __syncthreads();  // as becomes the result tile
+  float s1 = 0.f, s2 = 0.f, pivot = 0.f;
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) {
+    int t = t0 + o;
+    if (t < T) {
+      float v = acc[o];
+      if constexpr (XB) v = __builtin_bit_cast(float, (unsigned)dw_bf16(v) << 16);  // (the stored value)
+      as[(wave * RUN + o) * 64 + lane] = v;
+      if (STATS) {
+        if (o == 0) pivot = v;
+        const float d = v - pivot;
+        s1 += d;
+        s2 += d * d;
+      }
+    }
+  }
+  if (STATS)
+    dwg_stats(reinterpret_cast<float(*)[2][64]>(dwg_lds + ROWS * 64), partial, s1, s2, pivot, T, tbase, t0, C, c, true,
+              lane, wave);
+  else
+    __syncthreads();
+  const int sub = tid & 7;
+#pragma unroll
+  for (int r = tid >> 3; r < TT; r += 32) {
+    const int t = tbase + r;
+    if (t < T) dw_st8_global<XB>(y, ((long long)b * T + t) * C + c0 + 8 * sub, &as[r * 64 + 8 * sub]);
+  }
+}
+
+// the variants of dwconv_glu_bwd_tile_kernel
+template <bool XB>
+__global__ __launch_bounds__(256) void dwconv_glu_bwd_tile_generic_kernel(const void* __restrict__ dy,
+                                                                           const void* __restrict__ x, int ldx,
+                                                                           const float* __restrict__ w,
+                                                                           void* __restrict__ dxv,
+                                                                           float* __restrict__ partial, int B, int T,
+                                                                           int C, int dx_b, int K) {
+  // as [ROWS][64] (then: da, [4 RUN][64]) | gs [ROWS][64] (then: red)
+  extern __shared__ __attribute__((aligned(16))) float dwg_lds[];
+  const int PAD = (K - 1) / 2, ROWS = dwg_rows(K), TT = 4 * RUN;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c0 = blockIdx.x * 64, c = c0 + lane;
+  const int tbase = blockIdx.y * TT;
+  const int b = blockIdx.z;
+  float *as = dwg_lds, *gs = dwg_lds + ROWS * 64;
+  dwg_stage8<XB>(as, gs, x, dy, ldx, b, T, C, c0, tbase, PAD, ROWS, tid);
+  __syncthreads();
+  float da[RUN], gy[RUN];
+  dwg_dgrad(gs + wave * RUN * 64 + lane, w, C, c, true, K, da);
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) gy[o] = gs[(wave * RUN + o + PAD) * 64 + lane];
+  __syncthreads();  // gs becomes the tap-gradient reduction buffer
+  dwg_wgrad(as + wave * RUN * 64 + lane, gy, gs, partial, (long long)b * gridDim.y + blockIdx.y, C, c, true, K, lane,
+            wave);
+#pragma unroll
+  for (int o = 0; o < RUN; ++o) as[(wave * RUN + o) * 64 + lane] = da[o];
+  __syncthreads();
+  // dx = (da * s, da * v * s * (1 - s)) by rows, 16 bytes per lane; value and gate read again (L2), the sigmoid
+  // recomputed: the values of dwconv_glu_bwd_tile_kernel
+  const int sub = tid & 7;
+#pragma unroll
+  for (int r = tid >> 3; r < TT; r += 32) {
+    const int t = tbase + r;
+    if (t < T) {
+      const long long row = ((long long)b * T + t) * ldx + c0 + 8 * sub;
+      float v8[8], g8[8], d8[8], h8[8];
+      dw_ld8<XB>(x, row, v8);
+      dw_ld8<XB>(x, row + C, g8);
+      const float4 p = *reinterpret_cast<const float4*>(&as[r * 64 + 8 * sub]);
+      const float4 q = *reinterpret_cast<const float4*>(&as[r * 64 + 8 * sub + 4]);
+      const float dd[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float sc = fs2_sigmoid(g8[j]), vc = v8[j];
+        d8[j] = dd[j] * sc;
+        h8[j] = dd[j] * vc * sc * (1.f - sc);
+      }
+      if (dx_b) {
+        dw_st8_global_r<true>(dxv, row, d8);
+        dw_st8_global_r<true>(dxv, row + C, h8);
+      } else {
+        dw_st8_global_r<false>(dxv, row, d8);
+        dw_st8_global_r<false>(dxv, row + C, h8);
+      }
+    }
+  }
+}
+
+bool dw_force_generic() {  // FS2_DWCONV_GENERIC=1: every width on the run-time-K kernels (measurement and test aid)
+  const char* e = getenv("FS2_DWCONV_GENERIC");
+  return e && atoi(e) != 0;
+}
+bool dw_generic_width(int K) { return K >= 1 && K <= KMAX && (K & 1); }
+
 }  // namespace
 
 extern "C" int fs2hip_dwconv_blocks(int B, int T) { return B * ((T + 4 * RUN - 1) / (4 * RUN)); }
@@ -461,33 +847,51 @@ extern "C" int fs2hip_dwconv_fwd_b(const void* x, int ldx, const float* w, const
   const bool tiles_off = tile_env && atoi(tile_env) == 0;
   if (io_bf16 != 0 && io_bf16 != 1 && io_bf16 != 2) return FS2HIP_EINVAL;
   if (io_bf16 == 2 && (glu || stats)) return FS2HIP_EINVAL;
+  const int kk = dw_force_generic() ? 0 : K;  // 0: no instantiated width, i.e. the run-time-K kernels
+  const size_t shm = (size_t)(dwg_rows(K) * 64 + 4 * 2 * 64) * sizeof(float);
   if (glu && !tiles_off && (C % 64) == 0 && (ldx % 8) == 0 && ((uintptr_t)x % 16) == 0) {
 #define DW_FWD_T(KK)                                                                                              \
   if (io_bf16 && stats) dwconv_glu_fwd_tile_kernel<KK, true, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);        \
   else if (io_bf16) dwconv_glu_fwd_tile_kernel<KK, false, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);          \
   else if (stats) dwconv_glu_fwd_tile_kernel<KK, true, false><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);            \
   else dwconv_glu_fwd_tile_kernel<KK, false, false><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);
-    switch (K) {
+    switch (kk) {
       case 3: DW_FWD_T(3) break;
       case 5: DW_FWD_T(5) break;
       case 7: DW_FWD_T(7) break;
       case 9: DW_FWD_T(9) break;
       case 15: DW_FWD_T(15) break;
       case 31: DW_FWD_T(31) break;
-      default: return FS2HIP_EINVAL;
+      default:
+        if (!dw_generic_width(K)) return FS2HIP_EINVAL;
+        if (io_bf16 && stats) dwconv_glu_fwd_tile_generic_kernel<true, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+        else if (io_bf16) dwconv_glu_fwd_tile_generic_kernel<false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+        else if (stats) dwconv_glu_fwd_tile_generic_kernel<true, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+        else dwconv_glu_fwd_tile_generic_kernel<false, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
     }
 #undef DW_FWD_T
     FS2_LAUNCH_CHECK();
     return 0;
   }
-  switch (K) {
+  switch (kk) {
     case 3: DW_FWD(3) break;
     case 5: DW_FWD(5) break;
     case 7: DW_FWD(7) break;
     case 9: DW_FWD(9) break;
     case 15: DW_FWD(15) break;
     case 31: DW_FWD(31) break;
-    default: return FS2HIP_EINVAL;
+    default:
+      if (!dw_generic_width(K)) return FS2HIP_EINVAL;
+      if (io_bf16 == 2) {
+        dwconv_fwd_generic_kernel<false, false, false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+      } else if (io_bf16) {
+        if (!glu) return FS2HIP_EINVAL;
+        if (stats) dwconv_fwd_generic_kernel<true, true, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+        else dwconv_fwd_generic_kernel<true, false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+      } else if (glu && stats) dwconv_fwd_generic_kernel<true, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+      else if (glu) dwconv_fwd_generic_kernel<true, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+      else if (stats) dwconv_fwd_generic_kernel<false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
+      else dwconv_fwd_generic_kernel<false, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
   }
   FS2_LAUNCH_CHECK();
   return 0;
@@ -523,30 +927,46 @@ extern "C" int fs2hip_dwconv_bwd_b(const void* dy, const void* x, int ldx, const
   hipStream_t s = (hipStream_t)stream;
   const char* tile_env = getenv("FS2_DWCONV_TILE");  // "0": the per-thread-window kernels everywhere (measurement aid, tests)
   const bool tiles_off = tile_env && atoi(tile_env) == 0;
+  const int kk = dw_force_generic() ? 0 : K;  // 0: no instantiated width, i.e. the run-time-K kernels
+  const size_t shm = (size_t)(2 * dwg_rows(K) * 64) * sizeof(float);
   if (glu && !tiles_off && (C % 64) == 0 && (ldx % 8) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
     if ((dx_bf16 & 2) && !(dx_bf16 & 1)) return FS2HIP_EINVAL;
 #define DW_BWD_T(KK)                                                                                              \
   if (dx_bf16 & 2) dwconv_glu_bwd_tile_kernel<KK, true><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C, 1); \
   else dwconv_glu_bwd_tile_kernel<KK, false><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C, dx_bf16 & 1);
-    switch (K) {
+    switch (kk) {
       case 3: DW_BWD_T(3) break;
       case 5: DW_BWD_T(5) break;
       case 7: DW_BWD_T(7) break;
       case 9: DW_BWD_T(9) break;
       case 15: DW_BWD_T(15) break;
       case 31: DW_BWD_T(31) break;
-      default: return FS2HIP_EINVAL;
+      default:
+        if (!dw_generic_width(K)) return FS2HIP_EINVAL;
+        if (dx_bf16 & 2) dwconv_glu_bwd_tile_generic_kernel<true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, 1, K);
+        else dwconv_glu_bwd_tile_generic_kernel<false><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, dx_bf16 & 1, K);
     }
 #undef DW_BWD_T
   } else {
-    switch (K) {
+    switch (kk) {
       case 3: DW_BWD(3) break;
       case 5: DW_BWD(5) break;
       case 7: DW_BWD(7) break;
       case 9: DW_BWD(9) break;
       case 15: DW_BWD(15) break;
       case 31: DW_BWD(31) break;
-      default: return FS2HIP_EINVAL;
+      default:
+        if (!dw_generic_width(K)) return FS2HIP_EINVAL;
+        if (dx_bf16 & 2) {
+          if (!glu || !(dx_bf16 & 1)) return FS2HIP_EINVAL;
+          dwconv_bwd_generic_kernel<true, true, true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
+        } else if (dx_bf16) {
+          if (glu) dwconv_bwd_generic_kernel<true, true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
+          else dwconv_bwd_generic_kernel<false, true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
+        } else {
+          if (glu) dwconv_bwd_generic_kernel<true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
+          else dwconv_bwd_generic_kernel<false><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
+        }
     }
   }
   FS2_LAUNCH_CHECK();

@@ -1591,6 +1591,16 @@ class StatParts:
         self.partial, self.nparts, self.part_rows, self.group_rows, self.count = partial, nparts, part_rows, group_rows, count
 
 
+#: depthwise convolution widths: every odd K up to DWCONV_K_MAX (3, 5, 7, 9, 15 and 31 on kernels instantiated for
+#: them, the rest on the run-time-K kernels of conv.hip)
+DWCONV_K_MAX = 63
+DWCONV_WIDTHS = f"depthwise kernel sizes are odd, 1 to {DWCONV_K_MAX}"
+
+
+def dwconv_width_ok(k) -> bool:
+    return isinstance(k, int) and 1 <= k <= DWCONV_K_MAX and k % 2 == 1
+
+
 def dwconv_fwd(x, w, bias, B, T, *, glu=False, stats=False, out_dtype=None):
     """x [B*T, C or 2C] -> y [B, T, C]; w [K, C].  Returns (y, StatParts or None).  A bf16 ``x`` (GLU form; bf16
     activation storage) gives a bf16 ``y`` whose statistics are those of the rounded values.  ``out_dtype`` bf16 with an
@@ -1601,6 +1611,7 @@ def dwconv_fwd(x, w, bias, B, T, *, glu=False, stats=False, out_dtype=None):
     yb_only = out_dtype == torch.bfloat16 and not xb
     _req(not yb_only or not (glu or stats), "dwconv_fwd: fp32 -> bf16 is the plain form without statistics")
     K, Cc = w.shape
+    _req(dwconv_width_ok(K), f"dwconv_fwd: kernel size {K}; {DWCONV_WIDTHS}")
     ldx = x.shape[-1]
     _req(_rows(x) == B * T and ldx == (2 * Cc if glu else Cc), "dwconv_fwd: shape mismatch")
     if bias is not None:
@@ -1622,6 +1633,7 @@ def dwconv_bwd(dy, x, w, dw, dbias, B, T, *, glu=False, out_dtype=torch.float32)
     _chk(w, name="w"); _chk(dw, name="dw")
     _req(not xb or (glu and out_dtype == torch.bfloat16), "dwconv_bwd: bf16 inputs need the GLU form and a bf16 result")
     K, Cc = w.shape
+    _req(dwconv_width_ok(K), f"dwconv_bwd: kernel size {K}; {DWCONV_WIDTHS}")
     ldx = x.shape[-1]
     _req(_rows(x) == B * T and ldx == (2 * Cc if glu else Cc) and dy.numel() == B * T * Cc and dw.numel() == K * Cc,
          "dwconv_bwd: shape mismatch")

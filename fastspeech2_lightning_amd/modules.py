@@ -423,12 +423,10 @@ class ConvModule:
     """LayerNorm -> Conv1d(D,2D,1) -> GLU -> depthwise Conv1d(k) -> BatchNorm1d -> SiLU -> Conv1d(D,D,1)
     -> Dropout; y = x + f(x)."""
 
-    KERNEL_SIZES = (3, 5, 7, 9, 15, 31)  # depthwise-convolution widths the kernels are instantiated for
-
     def __init__(self, S, env: Env, prefix, d, k, p, dims_ok=False):
         self.dims_ok = dims_ok
-        if k not in self.KERNEL_SIZES:
-            raise ValueError(f"Conformer convolution module: depthwise kernel size {k}; this build carries {self.KERNEL_SIZES}")
+        if not H.dwconv_width_ok(k):
+            raise ValueError(f"Conformer convolution module: depthwise kernel size {k}; {H.DWCONV_WIDTHS}")
         self.S, self.env, self.p, self.k, self.d = S, env, p, k, d
         self.ln = LayerNorm(S, prefix + "layer_norm.", d)
         q = prefix + "sequential."
@@ -586,6 +584,8 @@ class VariancePredictor:
     def __init__(self, S, env: Env, prefix, d_in, cfg):
         self.S, self.env = S, env
         self.depthwise, self.k, self.p, self.c = cfg.depthwise, cfg.kernel_size, cfg.dropout, cfg.input_dim
+        if cfg.depthwise and not H.dwconv_width_ok(self.k):  # (an even width's "same" padding drops a frame)
+            raise ValueError(f"variance predictor {prefix!r}: depthwise kernel size {self.k}; {H.DWCONV_WIDTHS}")
         self.layers = []
         for i in range(cfg.n_layers):
             cin = d_in if i == 0 else cfg.input_dim
