@@ -137,7 +137,7 @@ __device__ __forceinline__ void fin_parts(const float* __restrict__ partial, int
 // rows of part p (bn_finalize): the parts tile groups of group_rows rows (one group = the whole matrix for colstats,
 // one utterance for the depthwise conv's fused statistics) in stripes of part_rows
 
-// stats layout (per channel): [0]=scale (gamma*invstd) [1]=shift (beta-mean*scale) [2]=mean [3]=invstd
+// stats layout (per channel): [0]=scale (gamma*invstd) [1]=shift (beta-mean*scale) [2]=mean [3]=invstd [4]=eps
 // training: Chan's parallel merge of the per-part (n, mean, M2) in fp64 -- mean = sum n_p mean_p / N, then
 // M2 = sum [M2_p + n_p (mean_p - mean)^2]
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ partial, int nparts,
@@ -181,6 +181,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
   stats[1 * C + c] = beta[c] - mean * sc;
   stats[2 * C + c] = mean;
   stats[3 * C + c] = invstd;
+  stats[4 * C + c] = eps;  // (read by bn_bwd_small_kernel, which recomputes the variance in fp64)
 }
 
 // four fp32 -> four bf16 (round to nearest even), 8 bytes
@@ -322,6 +323,47 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const void* __restric
   }
 }
 
+// Training-mode backward of a batch of FEW rows (the last GST convolution sees B * 2 of them), one thread per channel,
+// in fp64.  dy = scale * (dz - mean(dz) - xhat * mean(dz * xhat)) removes from dz its components along 1 and xhat: with
+// M rows that leaves M - 2 of M dimensions, and with two rows nothing but (dz_0 - dz_1) / 2 * eps / (var + eps) --
+// terms of size 1 cancelling to 1e-3 or less, of which the fp32 kernels above (fp32 mean and invstd, fp32 xhat) keep
+// three digits.  Here mean and variance are taken again from y in fp64, so xhat, both means and the difference carry
+// fp64 rounding; dz itself (and the activation's argument, which must decide as the forward pass did) stays fp32.
+constexpr int BN_SMALL_ROWS = 16;
+__global__ __launch_bounds__(64) void bn_bwd_small_kernel(const float* __restrict__ dout, const float* __restrict__ y,
+                                                           const float* __restrict__ stats, float* __restrict__ dgamma,
+                                                           float* __restrict__ dbeta, float* __restrict__ dy, int M, int C,
+                                                           int act, Fs2Drop drop_in) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  const Fs2Drop drop = fs2_resolve_drop(drop_in);
+  const float sc = stats[c], sh = stats[C + c];
+  const double eps = (double)stats[4 * C + c];
+  double mu = 0.0, m2 = 0.0;
+  for (int r = 0; r < M; ++r) mu += (double)y[(long long)r * C + c];
+  mu /= (double)M;
+  for (int r = 0; r < M; ++r) {
+    const double d = (double)y[(long long)r * C + c] - mu;
+    m2 += d * d;
+  }
+  const double invstd = 1.0 / sqrt(m2 / (double)M + eps);
+  double s1 = 0.0, s2 = 0.0;
+  for (int r = 0; r < M; ++r) {
+    const long long idx = (long long)r * C + c;
+    const double dz = (double)dz_of(dout[idx], y[idx], sc, sh, act, drop, (unsigned long long)idx);
+    s1 += dz;
+    s2 += dz * (((double)y[idx] - mu) * invstd);
+  }
+  dbeta[c] = (float)s1;
+  dgamma[c] = (float)s2;
+  const double k1 = s1 / (double)M, k2 = s2 / (double)M;
+  for (int r = 0; r < M; ++r) {
+    const long long idx = (long long)r * C + c;
+    const double dz = (double)dz_of(dout[idx], y[idx], sc, sh, act, drop, (unsigned long long)idx);
+    dy[idx] = (float)((double)sc * (dz - k1 - ((double)y[idx] - mu) * invstd * k2));
+  }
+}
+
 bool wide_ok(int C, WideMap& wm) {
   if ((C % 4) || C > 1024) return false;
   wm.tpr = C / 4;
@@ -420,6 +462,12 @@ extern "C" int fs2hip_bn_act_bwd_b(const void* dout, const void* y, const float*
     return FS2HIP_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
+  if (training && M <= BN_SMALL_ROWS && !(in_bf16 & 3) && dy && !dy_bf16) {
+    bn_bwd_small_kernel<<<dim3((C + 63) / 64), dim3(64), 0, s>>>((const float*)dout, (const float*)y, stats, dgamma, dbeta,
+                                                              dy, M, C, act, drop);
+    FS2_LAUNCH_CHECK();
+    return 0;
+  }
   const int nparts = fs2hip_colstats_parts(M);
 #define FS2_BN_RED(IB_, DB_) bn_bwd_reduce_kernel<IB_, DB_><<<dim3(nparts), dim3(256), 0, s>>>(dout, y, stats, M, C, act, drop, partial, wm)
   switch (in_bf16 & 3) {

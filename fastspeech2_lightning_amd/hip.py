@@ -1669,7 +1669,7 @@ def colstats(y) -> StatParts:
 
 def bn_finalize(parts: Optional[StatParts], gamma, beta, running_mean, running_var, *, momentum=0.1, eps=1e-5,
                 training=True):
-    """Returns stats [4, C] = (scale, shift, mean, invstd); updates the running buffers when training.
+    """Returns stats [5, C] = (scale, shift, mean, invstd, eps); updates the running buffers when training.
     ``parts``: the batch statistics (``colstats`` / ``dwconv_fwd(stats=True)``); None in evaluation mode."""
     _chk(gamma, name="gamma"); _chk(beta, name="beta")
     Cc = gamma.numel()
@@ -1683,7 +1683,7 @@ def bn_finalize(parts: Optional[StatParts], gamma, beta, running_mean, running_v
     if running_mean is not None:
         _chk(running_mean, name="running_mean"); _chk(running_var, name="running_var")
         _req(running_mean.numel() == Cc and running_var.numel() == Cc, "bn_finalize: running stats size")
-    stats = torch.empty(4, Cc, device=gamma.device, dtype=torch.float32)
+    stats = torch.empty(5, Cc, device=gamma.device, dtype=torch.float32)
     _ok(lib().fs2hip_bn_finalize(_p(partial), nparts, count, part_rows, group_rows, _p(gamma), _p(beta),
                                  _p(running_mean), _p(running_var), momentum, eps, int(training), _p(stats), Cc,
                                  _stream()), "bn_finalize")
@@ -1696,7 +1696,7 @@ def bn_act_fwd(y, stats, act=None, drop: Drop = NO_DROP, bf16_copy=False, bf16_o
     yb = y.dtype == torch.bfloat16
     _chk(y, y.dtype if yb else torch.float32, "y"); _chk(stats, name="stats")
     M, Cc = _rows(y), y.shape[-1]
-    _req(stats.numel() == 4 * Cc, "bn_act_fwd: stats size")
+    _req(stats.numel() == 5 * Cc, "bn_act_fwd: stats size")
     out = None if bf16_only else torch.empty(y.shape, device=y.device, dtype=torch.float32)
     out_b = torch.empty(y.shape, device=y.device, dtype=torch.bfloat16) if (bf16_copy or bf16_only) else None
     _ok(lib().fs2hip_bn_act_fwd_b(_p(y), _p(stats), _p(out), _p(out_b), M, Cc, _ACT[act], drop.p, drop.seed,
@@ -1713,7 +1713,7 @@ def bn_act_bwd(dout, y, stats, dgamma, dbeta, act=None, drop: Drop = NO_DROP, tr
     for n, t in (("stats", stats), ("dgamma", dgamma), ("dbeta", dbeta)):
         _chk(t, name=n)
     M, Cc = _rows(y), y.shape[-1]
-    _req(dout.shape == y.shape and stats.numel() == 4 * Cc and dgamma.numel() == Cc and dbeta.numel() == Cc,
+    _req(dout.shape == y.shape and stats.numel() == 5 * Cc and dgamma.numel() == Cc and dbeta.numel() == Cc,
          "bn_act_bwd: shape mismatch")
     nparts = lib().fs2hip_colstats_parts(M)
     ws = _workspace(nparts * 2 * Cc + 2 * Cc, y.device)

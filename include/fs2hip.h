@@ -342,7 +342,7 @@ int fs2hip_dwconv_bwd_b(const void* dy, const void* x, int ldx, const float* w, 
 
 /* ------------------------------------------------------------------------------------
  * BatchNorm1d over the channels of [M][C] (+ activation + dropout), fs2/layers.py:204-212 and
- * the Conformer conv module.  stats is [4][C]: scale, shift, mean, invstd.
+ * the Conformer conv module.  stats is [5][C]: scale, shift, mean, invstd, eps.
  *   colstats   : partial[fs2hip_colstats_parts(M)][2][C] = per-stripe (mean, sum of squared
  *                deviations) over stripes of fs2hip_colstats_part_rows(M) rows, accumulated on
  *                pivot-shifted values (torch's BatchNorm is Welford: a plain E[x^2]-E[x]^2 in fp32
