@@ -4,9 +4,9 @@ MAS and durations are bit-exact; floating point at 2e-5 of scale (CTC gradient 1
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from oracle import fs2_oracle as O
+from tests.aligner_references import close, make_case, ref_attention
 
 pytestmark = pytest.mark.gpu
 
@@ -16,33 +16,6 @@ def H():
     from fastspeech2_lightning_amd import hip
     hip.lib()
     return hip
-
-
-def close(a, b, tol=2e-5, msg=""):
-    a, b = a.detach().cpu().double(), b.detach().cpu().double()
-    fin = torch.isfinite(b)
-    assert torch.equal(torch.isfinite(a), fin), msg + ": non-finite pattern"
-    scale = max(float(b[fin].abs().max()), 1e-6)
-    err = float((a[fin] - b[fin]).abs().max()) / scale
-    assert err < tol, f"{msg}: rel err {err:.3e}"
-
-
-def make_case(B=3, T1=37, T2=11, C=80, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    q, k = torch.randn(B, T1, C, generator=g) * 3, torch.randn(B, T2, C, generator=g) * 3
-    key_lens = torch.tensor([T2, max(2, T2 - 3), max(2, T2 // 2)][:B], dtype=torch.int32)
-    q_lens = torch.tensor([T1, T1 - 5, max(T2, T1 // 2)][:B], dtype=torch.int32)
-    prior = O.beta_binomial_prior(q_lens, key_lens, T1, T2)
-    return q, k, key_lens, q_lens, prior
-
-
-def ref_attention(q, k, key_lens, prior):
-    d = ((q[:, :, None, :] - k[:, None, :, :]) ** 2).sum(-1)
-    logits = -0.0005 * d
-    lp = F.log_softmax(logits, dim=2) + torch.log(prior + 1e-8)
-    mask = torch.arange(k.shape[1])[None, None, :] >= key_lens[:, None, None]
-    soft = F.softmax(lp.masked_fill(mask, -float("inf")), dim=2)
-    return logits, lp, soft
 
 
 def test_dist_softmax(H):

@@ -796,3 +796,82 @@ def test_colsum_grad_deferred(H):
     finally:
         H.drop_pending_reductions()
     assert not H._PENDING_REDUCTIONS and not H._PENDING_SLABS
+
+
+# rowdot_bwd: 16 rows per workgroup; from 8 workgroups on (every real step: M >= 128) the partial sums are reduced by
+# fs2_reduce_rows in one launch, below that by two reduce_slabs launches.
+@pytest.mark.parametrize("C", [256, 80])
+@pytest.mark.parametrize("B,T", [(7, 16), (8, 16), (3, 43), (32, 128), (32, 648)])
+def test_rowdot_reduction_branches(H, B, T, C):
+    M = B * T
+    nblk = H.lib().fs2hip_rowdot_blocks(M)
+    assert nblk == (M + 15) // 16
+    assert (nblk >= 8) == (M != 16 * 7), "the branch condition of fs2hip_rowdot_bwd moved"  # M = 112: reduce_slabs twice
+    g = torch.Generator().manual_seed(M + C)
+    x, w, b = rnd(B, T, C, seed=M), rnd(C, seed=C, scale=0.1), rnd(1, seed=3)
+    lens = torch.randint(1, T + 1, (B,), generator=g).to(torch.int32)
+    lens[0], lens[B // 2] = T, 0
+    dout = torch.randn(B, T, generator=g)
+    mask = torch.arange(T)[None, :] < lens[:, None]
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
+    ref = (xr @ wr + br) * mask
+    (ref * dout.double()).sum().backward()
+    out = H.rowdot_fwd(x.cuda(), w.cuda(), b.cuda(), lens.cuda(), B, T)
+    close(out, ref, msg="rowdot fwd")
+    assert bool((out.cpu()[~mask] == 0).all())
+    dw, db = torch.empty(C, device="cuda"), torch.empty(1, device="cuda")
+    dx = H.rowdot_bwd(dout.cuda(), x.cuda(), w.cuda(), lens.cuda(), dw, db, B, T)
+    close(dx, xr.grad, msg="dx")
+    close(dw, wr.grad, msg="dw")
+    close(db, br.grad, msg="dbias")
+    assert bool((dx.cpu()[~mask] == 0).all())
+
+
+# masked_loss: at most 1024 workgroups of 256 threads, so the mel loss at the benchmark size (32 x 648 x 80 = 1.66 M
+# elements) walks its grid-stride loop seven times; (32, 648, 1) is 81 workgroups, one pass.
+@pytest.mark.parametrize("kind", ["mse", "mae"])
+@pytest.mark.parametrize("B,T,Cc", [(32, 648, 80), (32, 648, 1)])
+def test_masked_loss_full_size(H, B, T, Cc, kind):
+    assert (B * T * Cc > 1024 * 256) == (Cc == 80)
+    g = torch.Generator().manual_seed(B * T * Cc)
+    lens = torch.randint(1, T + 1, (B,), generator=g).to(torch.int32)
+    lens[0], lens[5] = T, 0  # an utterance of length 0
+    mask = (torch.arange(T)[None, :] < lens[:, None])[..., None]
+    pred, tgt = torch.randn(B, T, Cc, generator=g), torch.randn(B, T, Cc, generator=g)
+    same = torch.rand(B, T, Cc, generator=g) < 0.1
+    pred[same] = tgt[same]  # |0| has gradient sign(0) = 0
+    pr = pred.double().requires_grad_(True)
+    fn = F.mse_loss if kind == "mse" else F.l1_loss
+    ref = fn(pr * mask, tgt.double() * mask) * 0.1
+    ref.backward()
+    slot = torch.zeros(1, device="cuda")
+    d = H.masked_loss(pred.cuda(), tgt.cuda(), lens.cuda(), B, T, Cc, kind=kind, weight=0.1, loss_out=slot)
+    close(slot, ref.detach().reshape(1), msg=f"{kind} value")
+    close(d, pr.grad, msg=f"{kind} grad")
+    dc = d.cpu()
+    assert bool((same & mask).any()) and bool((dc[same] == 0).all()), "gradient where pred == target"
+    assert bool((dc[~mask.expand_as(dc)] == 0).all()), "gradient beyond the utterance"
+    slot2 = torch.zeros(1, device="cuda")
+    assert H.masked_loss(pred.cuda(), tgt.cuda(), lens.cuda(), B, T, Cc, kind=kind, weight=0.1, loss_out=slot2,
+                         want_grad=False) is None
+    assert torch.equal(slot, slot2)
+
+
+@pytest.mark.parametrize("kind", ["mse", "mae"])
+def test_masked_loss_int_duration_target_full_size(H, kind):
+    """The duration loss' target form, log(int + 1), at 32 x 128 tokens with an empty utterance."""
+    B, T = 32, 128
+    g = torch.Generator().manual_seed(7)
+    lens = torch.randint(1, T + 1, (B,), generator=g).to(torch.int32)
+    lens[0], lens[9] = T, 0
+    mask = torch.arange(T)[None, :] < lens[:, None]
+    dur = torch.randint(0, 40, (B, T), generator=g).to(torch.int32)
+    pred = torch.randn(B, T, generator=g) + 1.5
+    pr = pred.double().requires_grad_(True)
+    fn = F.mse_loss if kind == "mse" else F.l1_loss
+    ref = fn(pr * mask, torch.log(dur.double() + 1) * mask) * 0.1
+    ref.backward()
+    slot = torch.zeros(1, device="cuda")
+    d = H.masked_loss(pred.cuda(), dur.cuda(), lens.cuda(), B, T, 1, kind=kind, weight=0.1, loss_out=slot)
+    close(slot, ref.detach().reshape(1), msg=f"{kind} duration value")
+    close(d, pr.grad, msg=f"{kind} duration grad")
