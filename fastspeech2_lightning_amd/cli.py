@@ -121,7 +121,13 @@ def build_parser() -> argparse.ArgumentParser:
                          "tiles of the heaviest shapes tried inside the replayed step; ~30-60 s; -1...2 %% per step).  "
                          "Weights, optimizer state and BatchNorm buffers are restored afterwards; one rank only.  Save the "
                          "table with FS2_GEMM_TILE_CACHE=<file> to reuse it")
-    tr.add_argument("--dry-run", action="store_true", help="resolve config, filelists, look-up tables and the run directory, print the plan, touch no GPU")
+    tr.add_argument("--bucket-lengths", type=int, nargs="?", const=0, default=None, metavar="N",
+                    help="length-bucketed training batches: utterances of similar mel length share a batch, and every batch is "
+                         "padded (on the GPU) to its bucket's geometry, so that steps replay their launch plans on ragged "
+                         "data.  N = number of buckets (default: the launch-plan limit FS2_PLAN_MAX).  Off by default")
+    tr.add_argument("--dry-run", action="store_true", help="resolve config, filelists, look-up tables and the run directory, print the plan, touch no GPU "
+                                                             "(with --bucket-lengths: also reads every item's lengths once and writes the cache "
+                                                             "<run dir>/lengths.json, then prints the bucket table)")
     bm = sub.add_parser("benchmark", help="Time the forward pass on one batch of the training filelist (reference fs2/cli/benchmark.py)")
     bm.add_argument("config_file", type=Path)
     bm.add_argument("-c", "--config-args", action="append", default=[], metavar="KEY=VALUE")
@@ -160,6 +166,33 @@ def plan(args) -> dict:
                 val_rows=val_rows, run_dir=out, ckpt_dir=ckpt_dir, resume=resume,
                 max_steps=args.max_steps if args.max_steps is not None else t.max_steps,
                 max_epochs=args.max_epochs if args.max_epochs is not None else t.max_epochs)
+
+
+def bucket_count(args) -> Optional[int]:
+    """``--bucket-lengths [N]``: None = off, otherwise the number of buckets (no value: the launch-plan limit).  More
+    buckets than plans are allowed but warned about once: the limit is not raised (a plan's pool is gigabytes)."""
+    n = getattr(args, "bucket_lengths", None)
+    if n is None:
+        return None
+    from .plan import MAX_PLANS
+    if n < 0:
+        raise SystemExit("--bucket-lengths expects a positive bucket count")
+    n = n or MAX_PLANS
+    if n > MAX_PLANS and int(os.environ.get("RANK", 0)) == 0:
+        print(f"warning: --bucket-lengths {n} exceeds the launch-plan limit FS2_PLAN_MAX={MAX_PLANS}: the least recently "
+              "used plans will be dropped and recorded again (thrashing); use fewer buckets or raise FS2_PLAN_MAX",
+              file=sys.stderr, flush=True)
+    return n
+
+
+def bucket_report(p: dict, args, n_buckets: int) -> dict:
+    """What ``--dry-run --bucket-lengths`` adds to the plan: every bucket's geometry, item count and batches per epoch, and
+    the padded share of the epoch's mel frames with and without bucketing.  Reads the lengths (cached next to the run)."""
+    from .data import FeatureDataset, LengthBucketBatchSampler
+    ds = FeatureDataset(p["train_rows"], p["config"], p["lang2id"], p["speaker2id"])
+    lengths = ds.lengths(p["run_dir"] / "lengths.json")
+    sampler = LengthBucketBatchSampler(lengths, p["config"].training.batch_size, n_buckets, seed=args.seed, epoch=0)
+    return sampler.describe()
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -211,6 +244,7 @@ class Trainer:
             self.model.data_parallel(self.sync, rank)
             self.opt.grad_scale = self.sync.grad_scale
         self._tiles_shared = world == 1
+        self.n_buckets = bucket_count(args)
         cfg = self.model.config
         self.train_set = FeatureDataset(p["train_rows"], cfg, self.model.lang2id, self.model.speaker2id)
         self.val_set = FeatureDataset(p["val_rows"], cfg, self.model.lang2id, self.model.speaker2id)
@@ -228,6 +262,8 @@ class Trainer:
 
         from .data import collate
         cfg = self.model.config
+        if shuffle and self.n_buckets:
+            return self.bucketed_loader(dataset, epoch, workers, skip_batches)
         if self.world > 1:
             sampler = torch.utils.data.distributed.DistributedSampler(dataset, self.world, self.rank, shuffle=shuffle,
                                                                       seed=self.args.seed, drop_last=False)
@@ -240,6 +276,22 @@ class Trainer:
         return torch.utils.data.DataLoader(
             dataset, batch_sampler=batches, num_workers=workers,
             collate_fn=partial(collate, learn_alignment=cfg.model.learn_alignment, pin_memory=workers == 0))
+
+    def bucketed_loader(self, dataset, epoch: int, workers: int, skip_batches: int = 0):
+        """``--bucket-lengths``: the same promise as ``loader`` (an order that depends only on (seed, epoch, world)) with
+        batches of similar length; ``collate`` pads on the host as always, the batch carries its bucket's geometry and the
+        training step pads it to that on the GPU."""
+        from functools import partial
+
+        from .data import BucketedDataset, LengthBucketBatchSampler, collate_bucketed
+        cfg = self.model.config
+        cache = self.p["run_dir"] / "lengths.json"
+        lengths = dataset.lengths(cache, write=self.rank == 0)
+        sampler = LengthBucketBatchSampler(lengths, cfg.training.batch_size, self.n_buckets, seed=self.args.seed, epoch=epoch,
+                                           world=self.world, rank=self.rank, skip_batches=skip_batches)
+        return torch.utils.data.DataLoader(
+            BucketedDataset(dataset, sampler), batch_sampler=sampler.batches(), num_workers=workers,
+            collate_fn=partial(collate_bucketed, learn_alignment=cfg.model.learn_alignment, pin_memory=workers == 0))
 
     def batches(self, dataset, shuffle, epoch, workers, skip_batches: int = 0):
         from .data import DevicePrefetcher
@@ -279,6 +331,7 @@ class Trainer:
         rec["training/total_loss"] = float(slots[len(LOSS_KEYS)])
         r = self.opt.record()
         rec.update(lr=r["lr"], grad_norm=r["grad_norm"])
+        rec.update(self.model.plans.counters())  # steps replayed from / recorded into a launch plan, or run eagerly
         self.log(rec)
 
     def validate(self) -> float:
@@ -469,7 +522,9 @@ def gather_from_ranks(procs: list, queue, n: int, timeout: float = 300.0, poll_s
 def train(args, argv) -> int:
     p = plan(args)
     if args.dry_run:
+        n_buckets = bucket_count(args)
         print(json.dumps({
+            **({"bucket_lengths": bucket_report(p, args, n_buckets)} if n_buckets else {}),
             "config": str(args.config_file), "run_dir": str(p["run_dir"]), "resume": str(p["resume"]) if p["resume"] else None,
             "train_utterances": len(p["train_rows"]), "validation_utterances": len(p["val_rows"]),
             "lang2id": p["lang2id"], "speaker2id": p["speaker2id"], "batch_size": p["config"].training.batch_size,

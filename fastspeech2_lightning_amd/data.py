@@ -47,6 +47,50 @@ class FeatureDataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.entries)
 
+    def _names(self) -> list:
+        return [SEP.join([e["basename"], e.get("speaker", "default"), e.get("language", "default")]) for e in self.entries]
+
+    def lengths(self, cache=None, write: bool = True) -> list:
+        """``[(text_len, mel_len), ...]`` of every item, for ``LengthBucketBatchSampler``.  The text length is the encoded
+        token count of the filelist row; the mel length is read from the item's spectrogram file -- once: the result is
+        kept on the dataset and, with ``cache`` (``<run dir>/lengths.json``), on disk as JSON keyed by
+        ``basename--speaker--language``.  A cache written for another filelist (another item count, or a name it does
+        not hold) or for another text representation (characters / phones, symbol count) is ignored and rewritten (``write=False``: only read -- the ranks other than the first)."""
+        import json
+
+        from .config import TargetTrainingTextRepresentationLevel as L
+        if getattr(self, "_lengths", None) is not None and len(self._lengths) == len(self.entries):
+            return self._lengths
+        names = self._names()
+        chars = self.config.model.target_text_representation_level == L.characters
+        level = ("characters" if chars else "phones") + f"/{len(self.text_processor.symbols)}"  # what the text lengths count
+        cache = Path(cache) if cache is not None else None
+        if cache is not None and cache.exists():
+            try:
+                with open(cache, encoding="utf8") as f:
+                    stored = json.load(f)
+                table = stored["lengths"]
+                if stored["n"] == len(names) and stored.get("text") == level and all(n in table for n in names):
+                    self._lengths = [(int(table[n][0]), int(table[n][1])) for n in names]
+                    return self._lengths
+            except (ValueError, KeyError, TypeError, IndexError):
+                pass  # unreadable: measured again below
+        spec = f"spec-{self.sampling_rate}-{self.spec_type}.pt"
+        out = []
+        for e in self.entries:
+            tokens = e["character_tokens" if chars else "phone_tokens"]
+            n_text = len(self.text_processor.encode_escaped_string_sequence(tokens))
+            mel = self._load(e["basename"], e.get("speaker", "default"), e.get("language", "default"), "spec", spec)
+            out.append((int(n_text), int(mel.shape[1])))
+        self._lengths = out
+        if cache is not None and write:
+            cache.parent.mkdir(parents=True, exist_ok=True)
+            tmp = cache.with_suffix(".tmp")
+            with open(tmp, "w", encoding="utf8") as f:
+                json.dump({"n": len(names), "text": level, "lengths": {n: list(l) for n, l in zip(names, out)}}, f)
+            tmp.replace(cache)
+        return out
+
     def __getitem__(self, index):
         from .config import TargetTrainingTextRepresentationLevel as L
 
@@ -121,6 +165,165 @@ def collate(items: list[dict], learn_alignment: bool = True, pin_memory: bool = 
         else:
             batch[key] = col
     batch.update(src_lens=src_lens, max_src_len=max_src, mel_lens=mel_lens, max_mel_len=max_mel)
+    return batch
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# length-bucketed batches: few batch geometries per epoch, so that training steps replay their launch plans (plan.py)
+# ----------------------------------------------------------------------------------------------------------------------
+class BucketBatch(list):
+    """The item indices of one batch, with the ``(Ts_b, Tm_b)`` it is padded to and the index of its bucket."""
+
+    def __init__(self, indices, geometry, bucket):
+        super().__init__(indices)
+        self.geometry, self.bucket = tuple(geometry), int(bucket)
+
+
+class LengthBucketBatchSampler:
+    """Batches of items of similar length, each padded to its BUCKET's geometry instead of to its own maxima.
+
+    ``lengths``: every item's ``(text_len, mel_len)``.  The items sorted by mel length are cut into ``n_buckets``
+    contiguous ranges at the quantiles (about equally many items each; neighbours that end up with one geometry are
+    merged); a bucket's geometry ``(Ts_b, Tm_b)`` is the maxima over its members, rounded up to ``step``.  Every epoch a
+    bucket's members are shuffled and cut into batches of ``batch_size`` -- the leftover items form one short batch, no
+    item is dropped -- and the batches of all buckets are shuffled together.  An epoch therefore shows at most
+    ``2 * n_buckets`` distinct ``(B, Ts_b, Tm_b)``, where random batches padded to their own maxima show nearly as many
+    as there are batches.
+
+    The order depends only on ``(seed, epoch, world)``.  With ``world > 1`` the batches are laid out in rows of
+    ``world``, one batch per rank: rows are filled with full batches of ONE bucket as far as they go (the ranks of a
+    row then run the same geometry), the remaining batches share rows, and the last row is completed by repeating its
+    own batches (fewer than ``world`` repeats), so that every rank takes the same number of steps -- the per-bucket
+    gradient exchange would deadlock otherwise.  ``skip_batches`` drops the first batches of this rank's list (a resumed
+    epoch).  Iterating yields ``BucketBatch`` lists; ``geometry_of(index)`` is what ``BucketedDataset`` attaches to items.
+    """
+
+    def __init__(self, lengths, batch_size: int, n_buckets: Optional[int] = None, seed: int = 0, epoch: int = 0,
+                 world: int = 1, rank: int = 0, step: int = 1, skip_batches: int = 0):
+        if n_buckets is None:
+            from .plan import MAX_PLANS
+            n_buckets = MAX_PLANS
+        if batch_size < 1 or n_buckets < 1 or step < 1 or world < 1 or not 0 <= rank < world:
+            raise ValueError("LengthBucketBatchSampler: batch_size, n_buckets, step >= 1 and 0 <= rank < world")
+        self.lengths = [(int(t), int(m)) for t, m in lengths]
+        self.batch_size, self.n_buckets, self.step = int(batch_size), int(n_buckets), int(step)
+        self.seed, self.epoch, self.world, self.rank, self.skip_batches = int(seed), int(epoch), int(world), int(rank), int(skip_batches)
+        n = len(self.lengths)
+        order = sorted(range(n), key=lambda i: (self.lengths[i][1], self.lengths[i][0], i))
+        up = lambda v: -(-v // self.step) * self.step  # noqa: E731
+        self.buckets = []   # [(geometry, [item indices])], shortest first
+        for k in range(self.n_buckets):
+            members = order[k * n // self.n_buckets:(k + 1) * n // self.n_buckets]
+            if not members:
+                continue
+            geo = (up(max(self.lengths[i][0] for i in members)), up(max(self.lengths[i][1] for i in members)))
+            if self.buckets and self.buckets[-1][0] == geo:
+                self.buckets[-1][1].extend(members)
+            else:
+                self.buckets.append((geo, list(members)))
+        self._geometry = [None] * n
+        for geo, members in self.buckets:
+            for i in members:
+                self._geometry[i] = geo
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def geometry_of(self, index: int) -> tuple:
+        return self._geometry[index]
+
+    def rows(self) -> list:
+        """The epoch as rows of ``world`` batches (row i, column r = rank r's i-th batch)."""
+        g = torch.Generator().manual_seed(self.seed + self.epoch)
+        W, rows, loose = self.world, [], []
+        for b, (geo, members) in enumerate(self.buckets):
+            perm = [members[j] for j in torch.randperm(len(members), generator=g).tolist()]
+            batches = [BucketBatch(perm[i:i + self.batch_size], geo, b) for i in range(0, len(perm), self.batch_size)]
+            full = [x for x in batches if len(x) == self.batch_size]
+            whole = len(full) // W * W
+            rows += [full[i:i + W] for i in range(0, whole, W)]
+            loose += full[whole:] + [x for x in batches if len(x) != self.batch_size]
+        tail = None
+        for i in range(0, len(loose), W):
+            row = loose[i:i + W]
+            if len(row) < W:
+                tail = row + [row[j % len(row)] for j in range(W - len(row))]   # the evening-out repeats
+            else:
+                rows.append(row)
+        rows = [rows[j] for j in torch.randperm(len(rows), generator=g).tolist()]
+        if tail is not None:
+            rows.append(tail)
+        return rows
+
+    def batches(self) -> list:
+        """This rank's batches of the epoch, ``skip_batches`` dropped."""
+        return [row[self.rank] for row in self.rows()][self.skip_batches:]
+
+    def __iter__(self):
+        return iter(self.batches())
+
+    def __len__(self):
+        return max(len(self.rows()) - self.skip_batches, 0)
+
+    # -- what ``fs2l train --dry-run`` prints -------------------------------------------------------------------------
+    def padded_mel_rows(self) -> int:
+        """Mel rows (frames, padding included) of the epoch's batches over all ranks, evening-out repeats left out."""
+        seen, total = set(), 0
+        for row in self.rows():
+            for b in row:
+                if id(b) not in seen:
+                    seen.add(id(b))
+                    total += len(b) * b.geometry[1]
+        return total
+
+    def describe(self) -> dict:
+        real = sum(m for _, m in self.lengths)
+        table = [dict(Ts=geo[0], Tm=geo[1], items=len(members), full_batches=len(members) // self.batch_size,
+                      leftover_items=len(members) % self.batch_size,
+                      batches_per_epoch=-(-len(members) // self.batch_size)) for geo, members in self.buckets]
+        rand = random_batches(len(self.lengths), self.batch_size, self.seed + self.epoch)
+        plain = sum(len(b) * max(self.lengths[i][1] for i in b) for b in rand)
+        share = lambda padded: round(1.0 - real / padded, 4) if padded else 0.0  # noqa: E731
+        rows = self.rows()
+        return dict(n_buckets=len(self.buckets), buckets=table, batches_per_epoch_per_rank=len(rows),
+                    distinct_geometries=len({(len(b),) + b.geometry for row in rows for b in row}),
+                    padded_frame_share_bucketed=share(self.padded_mel_rows()),
+                    padded_frame_share_unbucketed=share(plain))
+
+
+def random_batches(n: int, batch_size: int, seed: int) -> list:
+    """The batches ``fs2l train`` draws without bucketing on one GPU (``RandomSampler`` + ``BatchSampler``)."""
+    sampler = torch.utils.data.RandomSampler(range(n), generator=torch.Generator().manual_seed(seed))
+    return list(torch.utils.data.BatchSampler(sampler, batch_size, drop_last=False))
+
+
+class BucketedDataset(torch.utils.data.Dataset):
+    """``dataset`` with every item tagged with its bucket's geometry (``collate_bucketed`` turns the tags of a batch into
+    the batch's ``bucket_geometry``): survives DataLoader workers, which only see indices."""
+
+    def __init__(self, dataset, sampler: LengthBucketBatchSampler):
+        self.dataset, self.sampler = dataset, sampler
+
+    def __len__(self):
+        return len(self.dataset)
+
+    def __getitem__(self, index):
+        item = dict(self.dataset[index])
+        item["bucket_geometry"] = self.sampler.geometry_of(index) + (self.sampler.batch_size,)
+        return item
+
+
+def collate_bucketed(items: list[dict], learn_alignment: bool = True, pin_memory: bool = False) -> dict:
+    """``collate`` -- unchanged: the batch is padded to its own maxima on the host -- plus ``bucket_geometry = (Ts_b,
+    Tm_b)``: the training step pads the device batch to it (``FastSpeech2.pad_batch``, one launch) -- and
+    ``bucket_leftover``: True for a bucket's short last batch, which the step runs eagerly and never records (one plan
+    per bucket: the leftovers of N buckets do not compete with the N full geometries for the plan cache)."""
+    batch = collate(items, learn_alignment=learn_alignment, pin_memory=pin_memory)
+    geos = batch.pop("bucket_geometry")
+    if any(tuple(g) != tuple(geos[0]) for g in geos):
+        raise ValueError("collate_bucketed: the items of a batch belong to different buckets")
+    batch["bucket_geometry"] = (int(geos[0][0]), int(geos[0][1]))
+    batch["bucket_leftover"] = len(items) != int(geos[0][2])
     return batch
 
 

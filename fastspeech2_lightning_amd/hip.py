@@ -151,6 +151,7 @@ SIGNATURES = {
     "fs2hip_gst_attn_bwd": "ppppppppiiip",
     "fs2hip_act_apply": "ppqip",
     "fs2hip_memset": "piqp",
+    "fs2hip_pad_batch": None,  # (const Fs2PadMember*, int, void*): set below
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -179,6 +180,7 @@ def lib():
         L.fs2hip_reduce_rows_multi.argtypes = [C.POINTER(ReduceJob), C.c_int, C.c_void_p]
         L.fs2hip_reduce_slabs_multi.argtypes = [C.POINTER(SlabJob), C.c_int, C.c_void_p]
         L.fs2hip_transpose_cast_bf16_multi.argtypes = [C.POINTER(TransposeJob), C.c_int, C.c_void_p]
+        L.fs2hip_pad_batch.argtypes = [C.POINTER(PadMember), C.c_int, C.c_void_p]
         L.fs2hip_plan_op_id.argtypes = [C.c_char_p]
         L.fs2hip_plan_events_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         L.fs2hip_plan_events_destroy.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -1850,6 +1852,97 @@ def masked_loss(pred, target, lens, B, T, Cc, *, kind="mse", weight=1.0, loss_ou
     _ok(lib().fs2hip_masked_loss(_p(pred), _p(tf), _p(ti), _p(lens), B, T, Cc, 0 if kind == "mse" else 1, weight,
                                  _p(dpred), _p(ws), _p(loss_out), _stream()), "masked_loss")
     return dpred
+
+
+# ------------------------------------------------------------------------------------------
+# device-side batch feed with padding (length-bucketed batches: data.LengthBucketBatchSampler)
+# ------------------------------------------------------------------------------------------
+PAD_MAX_MEMBERS = 16
+
+
+class PadMember(C.Structure):  # mirrors Fs2PadMember (include/fs2hip.h)
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("B", C.c_int), ("src0", C.c_int), ("src1", C.c_int),
+                ("dst0", C.c_int), ("dst1", C.c_int), ("pad_", C.c_int), ("row_bytes", C.c_longlong)]
+
+
+#: batch entries that run along the text axis ("s"), the mel axis ("m"); pitch / energy follow their level
+_PAD_AXES = {"text": "s", "pfs": "s", "mel": "m"}
+
+
+def pad_axes(batch: dict, frame_level=None) -> dict:
+    """{key: axes} of the batch's padded tensors: "s" = dimension 1 runs along the text, "m" = along the mel, "ms" = the
+    [B, Tm, Ts] attention prior of a learned-alignment model.  ``frame_level``: whether pitch / energy targets are
+    per frame (a bool, or {"pitch": bool, "energy": bool}); None reads it off the shapes and refuses a batch whose text
+    and mel lengths coincide (either reading would fit)."""
+    axes = {k: a for k, a in _PAD_AXES.items() if torch.is_tensor(batch.get(k))}
+    dur = batch.get("duration")
+    if torch.is_tensor(dur):
+        axes["duration"] = "ms" if dur.dim() == 3 else "s"
+    for k in ("pitch", "energy"):
+        v = batch.get(k)
+        if not torch.is_tensor(v):
+            continue
+        fl = frame_level.get(k) if isinstance(frame_level, dict) else frame_level
+        if fl is None:
+            Ts, Tm = batch["text"].shape[1], batch["mel"].shape[1]
+            _req(Ts != Tm, f"pad_batch: batch[{k!r}] could run along the text or the mel (both {Ts} long): pass frame_level")
+            _req(v.shape[1] in (Ts, Tm), f"pad_batch: batch[{k!r}] is neither text- nor mel-long")
+            fl = v.shape[1] == Tm
+        axes[k] = "m" if fl else "s"
+    return axes
+
+
+def padded_shape(shape, axes: str, Ts_b: int, Tm_b: int) -> tuple:
+    """Shape of a [B, axes..., inner...] tensor once its ``axes`` are padded to the geometry."""
+    if not axes:
+        return tuple(shape)
+    ext = [Tm_b if a == "m" else Ts_b for a in axes]
+    return (shape[0], *ext, *shape[1 + len(axes):])
+
+
+def pad_batch(batch: dict, Ts_b: int, Tm_b: int, out: Optional[dict] = None, frame_level=None) -> dict:
+    """The device batch (``FastSpeech2.prepare_batch``'s) padded with zeros to the bucket geometry ``(Ts_b, Tm_b)`` in ONE
+    launch (``fs2hip_pad_batch``): what ``data.collate`` would have produced had the batch's longest text been ``Ts_b``
+    tokens and its longest mel ``Tm_b`` frames.  Length vectors and ids are untouched; ``max_src_len`` / ``max_mel_len``
+    follow the geometry.  ``out`` None: the padded tensors are fresh and the others are passed through.  ``out`` = a
+    launch plan's recorded input tensors ({key: tensor}): EVERY tensor of ``out`` is written by the same launch (the
+    unpadded ones are plain copies), which is the whole feed of a replayed step."""
+    Ts_b, Tm_b = int(Ts_b), int(Tm_b)
+    axes = pad_axes(batch, frame_level)
+    keys = list(out) if out is not None else list(axes)
+    _req(0 < len(keys) <= PAD_MAX_MEMBERS, f"pad_batch: 1 to {PAD_MAX_MEMBERS} tensors per launch, got {len(keys)}")
+    members = (PadMember * len(keys))()
+    res = dict(batch)
+    for m, k in zip(members, keys):
+        src = batch.get(k)
+        if not torch.is_tensor(src):
+            raise ValueError(f"fs2hip: pad_batch: batch[{k!r}] is missing")
+        _chk(src, src.dtype, f"batch[{k!r}]")
+        ax = axes.get(k, "")
+        want = padded_shape(tuple(src.shape), ax, Ts_b, Tm_b)
+        _req(all(w >= s for w, s in zip(want, src.shape)),
+             f"pad_batch: batch[{k!r}] {tuple(src.shape)} does not fit the geometry (Ts {Ts_b}, Tm {Tm_b})")
+        if out is None:
+            dst = torch.empty(want, device=src.device, dtype=src.dtype)
+        else:
+            dst = _chk(out[k], src.dtype, f"out[{k!r}]")
+            _req(tuple(dst.shape) == want, f"pad_batch: out[{k!r}] is {tuple(dst.shape)}, the geometry needs {want}")
+        _req(src.numel() > 0, f"pad_batch: batch[{k!r}] is empty")
+        ext_s = [src.shape[1 + i] for i in range(len(ax))] + [1, 1]
+        ext_d = [want[1 + i] for i in range(len(ax))] + [1, 1]
+        inner = 1
+        for n in src.shape[1 + len(ax):]:
+            inner *= n
+        B = src.shape[0] if src.dim() else 1
+        m.src, m.dst, m.B = _p(src), _p(dst), B
+        m.src0, m.src1, m.dst0, m.dst1 = ext_s[0], ext_s[1], ext_d[0], ext_d[1]
+        m.row_bytes = inner * src.element_size()
+        res[k] = dst
+    _ok(lib().fs2hip_pad_batch(members, len(keys), _stream()), "pad_batch")
+    res["max_src_len"], res["max_mel_len"] = Ts_b, Tm_b
+    res.pop("bucket_geometry", None)
+    res.pop("bucket_leftover", None)
+    return res
 
 
 # ------------------------------------------------------------------------------------------

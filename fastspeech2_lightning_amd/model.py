@@ -849,13 +849,19 @@ class FastSpeech2(_Base):
         self.backward()
         return losses, output
 
-    def _plan_signature(self, batch):
+    def _plan_signature(self, batch, bucket=None):
         """Everything a recorded step's launch sequence depends on: the batch's geometry (tensor shapes, which optional
-        entries are there), and the model-side switches that choose kernels, streams or arguments.  None: not plannable."""
+        entries are there), and the model-side switches that choose kernels, streams or arguments.  None: not plannable.
+        ``bucket``: the ``(Ts_b, Tm_b)`` the batch is going to be padded to -- the shapes are then the padded ones."""
         if not (PL.ENABLED and self.plan_enabled and H.GEMM_PROFILE is None and not self.precision_overrides and H._REC is None
                 and self.variance_adaptor is not None) or torch.cuda.is_current_stream_capturing():
             return None
         geo = []
+        if bucket is not None:
+            axes = H.pad_axes(batch, self._frame_level_targets())
+            batch = dict(batch, max_src_len=int(bucket[0]), max_mel_len=int(bucket[1]))
+            for k, ax in axes.items():  # (meta tensors: shapes only)
+                batch[k] = torch.empty(H.padded_shape(tuple(batch[k].shape), ax, *bucket), device="meta")
         for k in sorted(batch):
             v = batch[k]
             if torch.is_tensor(v):
@@ -870,7 +876,25 @@ class FastSpeech2(_Base):
         return (tuple(geo), self.precision, bool(self.env.side_enabled), tuple(PRED_LANES.values()), id(sync) if sync else 0, bin_w, weights,
                 getattr(self.postnet, "dropout_p", None), M.BF16_CHAIN, M.PRED_STORED, M.POSTNET_IM2COL, FP32_TRANSPOSED, HOLD_WGRADS, EARLY_FLUSH, PRED_GROUP, M.WGRAD_GROUP_ROWS, H.GEMM_GROUP, self.env.seed, H.plan_flags())
 
+    def _frame_level_targets(self) -> dict:
+        """Whether the batch's pitch / energy targets run along the mel axis (they do for a model that learns the
+        alignment, whatever the predictors' level: fs2/variance_adaptor.py:269-279 averages them itself)."""
+        vp = self.config.model.variance_predictors
+        la = bool(self.config.model.learn_alignment)
+        return {"pitch": la or vp.pitch.level.value == "frame", "energy": la or vp.energy.level.value == "frame"}
+
+    def pad_batch(self, dev_batch, Ts_b, Tm_b):
+        """The prepared (device) batch padded with zeros to a length bucket's geometry in one launch
+        (``hip.pad_batch``): fresh tensors, ``max_src_len`` / ``max_mel_len`` following the geometry.  The step on the
+        result is the step on a batch whose longest text has ``Ts_b`` tokens and whose longest mel has ``Tm_b`` frames:
+        padding rows count in BatchNorm statistics and loss denominators exactly as the reference counts them."""
+        with torch.cuda.device(self.device_):
+            return H.pad_batch(self.prepare_batch(dev_batch), Ts_b, Tm_b, frame_level=self._frame_level_targets())
+
     def _planned_step(self, batch):
+        bucket = batch.get("bucket_geometry")  # (data.collate_bucketed: the batch is padded to it, on the device)
+        if bucket is not None:
+            return self._planned_step_bucketed(batch, bucket)
         sig = self._plan_signature(batch)
         if sig is None:
             return self._run_step(batch)
@@ -879,21 +903,54 @@ class FastSpeech2(_Base):
         if plan is not None:
             with torch.cuda.device(self.device_):
                 plan.feed(self.prepare_batch(batch))
-                losses, output = plan.replay(self.env.side_streams())
-            # the loss terms are handed out as a COPY of the recorded slot vector (one 32-byte ATen copy): Lightning keeps
-            # logged tensors and reads them later, and the next replay rewrites the recorded vector in place
-            slots = plan.extra["loss_slots"].clone()
-            losses = OrderedDict((k, slots[i]) for k, i in plan.extra["loss_index"])
-            self._loss_slots, self._hard_idx = slots, plan.extra["hard_idx"]
-            if plan.extra["bad"] is not None:
-                self._pending_bad.append((plan.extra["bad"], list(batch.get("basename") or [])))
-            plans.replayed += 1
-            return losses, output
+            return self._replay(plan, batch)
         if not plans.should_record(sig):
             plans.eager += 1
             return self._run_step(batch)
         with torch.cuda.device(self.device_):
             pb = self.prepare_batch(batch)
+        return self._record(sig, pb)
+
+    def _planned_step_bucketed(self, batch, bucket):
+        """A batch that carries a bucket geometry: looked up under the PADDED shapes; replayed with the whole feed --
+        padding included -- as one launch into the plan's recorded inputs, or padded once into fresh tensors for the
+        eager and the recorded step.  A bucket's short leftover batch (``bucket_leftover``) always runs eagerly and is
+        never counted towards recording: N buckets need N plans, and a leftover geometry that comes once per epoch does
+        not push a full batch's plan out of the cache."""
+        sig = self._plan_signature(batch, bucket)
+        plans = self.plans
+        if batch.get("bucket_leftover"):
+            plans.eager += sig is not None
+            return self._run_step(self.pad_batch(batch, *bucket))
+        plan = plans.lookup(sig) if sig is not None else None
+        if plan is not None:
+            with torch.cuda.device(self.device_):
+                plan.feed_padded(self.prepare_batch(batch), bucket, self._frame_level_targets())
+            return self._replay(plan, batch)
+        padded = self.pad_batch(batch, *bucket)
+        if sig is None:
+            return self._run_step(padded)
+        if not plans.should_record(sig):
+            plans.eager += 1
+            return self._run_step(padded)
+        return self._record(sig, padded)
+
+    def _replay(self, plan, batch):
+        with torch.cuda.device(self.device_):
+            losses, output = plan.replay(self.env.side_streams())
+        # the loss terms are handed out as a COPY of the recorded slot vector (one 32-byte ATen copy): Lightning keeps
+        # logged tensors and reads them later, and the next replay rewrites the recorded vector in place
+        slots = plan.extra["loss_slots"].clone()
+        losses = OrderedDict((k, slots[i]) for k, i in plan.extra["loss_index"])
+        self._loss_slots, self._hard_idx = slots, plan.extra["hard_idx"]
+        if plan.extra["bad"] is not None:
+            self._pending_bad.append((plan.extra["bad"], list(batch.get("basename") or [])))
+        self.plans.replayed += 1
+        return losses, output
+
+    def _record(self, sig, pb):
+        plans = self.plans
+        with torch.cuda.device(self.device_):
             inputs = {k: v for k, v in pb.items() if torch.is_tensor(v) and v.is_cuda}
             n_bad = len(self._pending_bad)
             plan, (losses, output) = PL.record(lambda: self._run_step(pb), inputs, self.device_)

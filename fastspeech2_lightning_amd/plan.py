@@ -13,7 +13,8 @@ device memory).  So:
   join events; host-side hand-offs that must happen at a fixed place in the sequence (a gradient bucket's all-reduce,
   ``parallel.GradSync``) are recorded as callbacks that split the plan into segments.  The step's allocations come from
   a ``torch.cuda.MemPool`` of the plan's own, so the recorded addresses stay reserved for it;
-* every later step of that geometry copies the batch into the recorded input tensors and calls
+* every later step of that geometry copies the batch into the recorded input tensors (a batch of a length bucket:
+  copied AND padded to the bucket's geometry by one ``fs2hip_pad_batch`` launch, ``StepPlan.feed_padded``) and calls
   ``fs2hip_plan_replay`` (csrc/plan.hip) once per segment: the host cost of the step is the ~5 us ``hipLaunchKernel``
   itself per launch.  The tensors the recorded step returned (losses, outputs) are the ones every replay writes.
 
@@ -245,6 +246,15 @@ class StepPlan:
                 raise PlanError(f"launch plan: batch[{k!r}] does not have the recorded geometry")
             dst.copy_(src, non_blocking=True)
 
+    def feed_padded(self, batch: dict, bucket, frame_level=None):
+        """The device batch of a length bucket into the recorded input tensors, zero padding included, as ONE launch
+        (``hip.pad_batch``) where ``feed`` issues a copy per tensor: the recorded tensors have the bucket's geometry,
+        the batch is padded to its own maxima."""
+        try:
+            H.pad_batch(batch, bucket[0], bucket[1], out=self.inputs, frame_level=frame_level)
+        except ValueError as e:
+            raise PlanError(f"launch plan: the batch does not fit the recorded geometry ({e})") from e
+
     def replay(self, side_streams=None):
         """``side_streams``: {raw handle: torch.cuda.Stream} of the model's side streams (host callbacks recorded under a
         side stream run under ``torch.cuda.stream`` of it)."""
@@ -306,6 +316,9 @@ class PlanCache:
     def __init__(self):
         self.plans, self.seen = {}, {}
         self.recorded = self.replayed = self.eager = 0
+
+    def counters(self) -> dict:
+        return dict(plans_replayed=self.replayed, plans_recorded=self.recorded, plans_eager=self.eager)
 
     def lookup(self, sig):
         p = self.plans.get(sig)

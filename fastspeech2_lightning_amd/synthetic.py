@@ -47,6 +47,37 @@ def synthetic_batch(B=2, ts_lo=48, ts_hi=64, n_symbols=64, n_mels=80, seed=1234,
     return batch
 
 
+def synthetic_lengths(n, ts_lo=20, ts_hi=160, dur_hi=9, seed=1234):
+    """``[(text_len, mel_len), ...]`` of ``n`` utterances drawn as ``synthetic_batch`` draws them (``src_lens ~
+    U{lo..hi}``, per-token durations ``U{1..dur_hi}``, ``mel_len`` = their total) without building the tensors: the ragged
+    epoch of a length-bucketing sampler (defaults: LJSpeech-like spread, 20-160 tokens, ~5 frames per token)."""
+    g = torch.Generator().manual_seed(seed)
+    src = torch.randint(ts_lo, ts_hi + 1, (n,), generator=g)
+    return [(int(t), int(torch.randint(1, dur_hi + 1, (int(t),), generator=g).sum())) for t in src]
+
+
+def synthetic_item(text_len, mel_len, n_symbols=64, n_mels=80, seed=0, learn_alignment=False, frame_level=False):
+    """One utterance as ``FeatureDataset.__getitem__`` returns it (the keys ``collate`` reads), with the given lengths:
+    durations are drawn to add up to ``mel_len`` (every token at least one frame, so ``mel_len >= text_len``)."""
+    if mel_len < text_len:
+        raise ValueError("synthetic_item: mel_len must be at least text_len")
+    g = torch.Generator().manual_seed(seed)
+    cuts = torch.randperm(mel_len - 1, generator=g)[:text_len - 1].sort().values + 1
+    edges = torch.cat([torch.zeros(1, dtype=torch.long), cuts, torch.tensor([mel_len])])
+    dur = (edges[1:] - edges[:-1]).to(torch.int32)
+    frames = learn_alignment or frame_level
+    n_var = mel_len if frames else text_len
+    item = dict(text=torch.randint(1, n_symbols, (text_len,), generator=g, dtype=torch.int32),
+                mel=torch.randn(mel_len, n_mels, generator=g), pitch=torch.randn(n_var, generator=g),
+                energy=torch.randn(n_var, generator=g), speaker_id=0, language_id=0, basename=f"utt{seed}",
+                mel_style_reference=None, pfs=None, duration_control=1.0)
+    if learn_alignment:
+        item["duration"] = beta_binomial_prior(torch.tensor([mel_len]), torch.tensor([text_len]), mel_len, text_len)[0]
+    else:
+        item["duration"] = dur
+    return item
+
+
 def beta_binomial_prior(mel_lens, src_lens, Tm, Ts, scaling=1.0):
     """Attention prior of the aligner's data pipeline (beta-binomial over text positions for each
     frame), zero padded to (B, Tm, Ts)."""

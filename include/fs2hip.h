@@ -553,6 +553,27 @@ int fs2hip_act_apply(const float* x, float* out, long long n, int act, void* str
  * every other entry point, which an ATen fill is not. */
 int fs2hip_memset(void* dst, int byte, long long nbytes, void* stream);
 
+/* The padding half of the reference's collate_method (fs2/dataset.py:257-293: every ragged column written into the
+ * top-left corner of a zero tensor) on the device, for a batch that is padded to a length bucket's geometry instead of
+ * to its own maxima: up to FS2_PAD_MAX_MEMBERS tensors in ONE launch.  A member is a dense tensor [B][src0][src1][row
+ * bytes] copied into the dense [B][dst0][dst1][row bytes]; every destination byte outside the source box becomes 0.
+ * An axis that is not padded has equal extents (a one-axis member: src1 == dst1 == 1); all extents equal is a plain
+ * copy, and src == dst with all extents equal is skipped.  Byte-wise: int32 / int64 token and duration tensors and fp32
+ * features alike.  The member table is passed by value in the kernel argument (nothing is uploaded; a launch plan keeps
+ * a host copy of it).  FS2HIP_EINVAL: n < 1 or n > FS2_PAD_MAX_MEMBERS, a null pointer, a non-positive extent, a
+ * destination extent smaller than the source's, overlapping source and destination. */
+#define FS2_PAD_MAX_MEMBERS 16
+typedef struct {
+  const void* src;
+  void* dst;
+  int B;
+  int src0, src1; /* source extents of the (up to) two padded axes */
+  int dst0, dst1; /* destination extents */
+  int pad_;
+  long long row_bytes; /* bytes of the contiguous inner row behind the padded axes */
+} Fs2PadMember;
+int fs2hip_pad_batch(const Fs2PadMember* members, int n, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
