@@ -516,13 +516,6 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnP p, const float*
   }
 }
 
-bool attn_args_ok(const void* qkv, int B, int T, int H, int HD) {
-  if (B <= 0 || T <= 0 || H <= 0) return false;
-  if (HD != 16 && HD != 32 && HD != 64 && HD != 128) return false;
-  if ((uintptr_t)qkv % 16) return false;
-  return true;
-}
-
 // measurement aid: first-generation kernels everywhere
 bool gen1_only() {
   static const bool v = getenv("FS2_ATTN_GEN1") != nullptr;
@@ -614,7 +607,7 @@ int attn_bwd_run(const float* qkv, const int* lens, const float* o, const float*
   return 0;
 }
 
-// scores: null (the dK/dV kernel recomputes K.Q^T) or fs2hip_attention_fwd_s's
+// scores: null (the dK/dV kernel recomputes K.Q^T) or the ones fs2hip_attention_fwd kept
 int attn_bwd_spill_run(const float* qkv, const int* lens, const float* o, const float* dout, const float* lse,
                        const float* scores, float* aux, float* ds, long long ds_floats, float* dqkv, int B, int T, int H,
                        int HDk, float scale, Fs2Drop drop, hipStream_t s) {
@@ -627,70 +620,20 @@ int attn_bwd_spill_run(const float* qkv, const int* lens, const float* o, const 
 
 bool aligned16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
+// What fs2hip_attention_fwd / _bwd refuse before a launcher sees the arguments, tensor alignment apart (the launchers check
+// the widths and sizes of scores and ds).  fp32_only: scores or ds given -- exact fp32 or "32-split", whose kernels on those
+// routes are the fp32 ones.
+bool attn_args_ok(int B, int T, int H, int HD, int operand_bf16, bool fp32_only) {
+  if (B <= 0 || T <= 0 || H <= 0 || fs2hip_attention_padded_dim(HD) == 0) return false;
+  return operand_bf16 >= 0 && operand_bf16 <= 2 && !(fp32_only && operand_bf16 == 1);
+}
+
 }  // namespace
-
-extern "C" int fs2hip_attention_fwd(const float* qkv, const int* lens, float* o, float* lse, int B, int T, int H,
-                                    int HD, float drop_p, unsigned long long drop_seed,
-                                    const unsigned long long* drop_step, int operand_bf16, void* stream) {
-  if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16)) return FS2HIP_EINVAL;
-  return attn_fwd_run(qkv, lens, o, lse, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step),
-                      operand_bf16, (hipStream_t)stream);
-}
-
-// The forward pass that also writes the masked scores out (operand_bf16 0: fp32 MFMA path, 2: "32-split"; head dims 64 / 128) for
-// fs2hip_attention_bwd_spill_s: `scores` holds at least B * H * T * (T rounded up to 32) floats.
-extern "C" int fs2hip_attention_fwd_s(const float* qkv, const int* lens, float* o, float* lse, float* scores,
-                                      long long score_floats, int B, int T, int H, int HD, float drop_p,
-                                      unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
-                                      void* stream) {
-  if (operand_bf16 != 0 && operand_bf16 != 2) return FS2HIP_EINVAL;  // exact fp32 or three exact bf16 planes
-  if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)scores % 16) || !scores) return FS2HIP_EINVAL;
-  return attn_fwd_s_run(qkv, lens, o, lse, scores, score_floats, B, T, H, HD, 1.f / sqrtf((float)HD),
-                        fs2_make_drop(drop_p, drop_seed, drop_step), operand_bf16, (hipStream_t)stream);
-}
 
 extern "C" int fs2hip_attention_bwd_spill_supported(int HD) {
   return (!gen1_only() && (HD == 64 || HD == 128)) ? 1 : 0;
 }
 
-extern "C" int fs2hip_attention_bwd_spill(const float* qkv, const int* lens, const float* o, const float* dout,
-                                          const float* lse, float* aux, float* ds, long long ds_floats, float* dqkv, int B,
-                                          int T, int H, int HD, float drop_p, unsigned long long drop_seed,
-                                          const unsigned long long* drop_step, void* stream) {
-  if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) ||
-      ((uintptr_t)ds % 16))
-    return FS2HIP_EINVAL;
-  return attn_bwd_spill_run(qkv, lens, o, dout, lse, nullptr, aux, ds, ds_floats, dqkv, B, T, H, HD, 1.f / sqrtf((float)HD),
-                            fs2_make_drop(drop_p, drop_seed, drop_step), (hipStream_t)stream);
-}
-
-extern "C" int fs2hip_attention_bwd(const float* qkv, const int* lens, const float* o, const float* dout,
-                                    const float* lse, float* delta, float* dqkv, int B, int T, int H, int HD,
-                                    float drop_p, unsigned long long drop_seed,
-                                    const unsigned long long* drop_step, int operand_bf16, void* stream) {
-  if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16))
-    return FS2HIP_EINVAL;
-  return attn_bwd_run(qkv, lens, o, dout, lse, delta, dqkv, B, T, H, HD, 1.f / sqrtf((float)HD),
-                      fs2_make_drop(drop_p, drop_seed, drop_step), operand_bf16, (hipStream_t)stream);
-}
-
-// fs2hip_attention_bwd_spill with the scores of fs2hip_attention_fwd_s: the dK/dV kernel reads them instead of recomputing
-// K.Q^T (3 products instead of 4, the forward pass's probabilities to the bit)
-extern "C" int fs2hip_attention_bwd_spill_s(const float* qkv, const int* lens, const float* o, const float* dout,
-                                            const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
-                                            float* dqkv, int B, int T, int H, int HD, float drop_p,
-                                            unsigned long long drop_seed, const unsigned long long* drop_step, void* stream) {
-  if (!attn_args_ok(qkv, B, T, H, HD) || ((uintptr_t)o % 16) || ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) ||
-      ((uintptr_t)ds % 16) || ((uintptr_t)scores % 16) || !scores)
-    return FS2HIP_EINVAL;
-  return attn_bwd_spill_run(qkv, lens, o, dout, lse, scores, aux, ds, ds_floats, dqkv, B, T, H, HD, 1.f / sqrtf((float)HD),
-                            fs2_make_drop(drop_p, drop_seed, drop_step), (hipStream_t)stream);
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Any head dimension 1..256: the kernels run at the padded width fs2hip_attention_padded_dim(HD) with the softmax scale of
-// the true one.  Zero columns of Q and K add exact zeros to every score, zero columns of V give zero output columns.
-// ------------------------------------------------------------------------------------------------------------------
 extern "C" int fs2hip_attention_padded_dim(int HD) {
   if (HD < 1 || HD > 256) return 0;
   int w = 16;
@@ -718,38 +661,36 @@ extern "C" int fs2hip_attention_unpad_heads(const float* src, float* dst, int ro
   return 0;
 }
 
-extern "C" int fs2hip_attention_fwd_hd(const float* qkv, const int* lens, float* o, float* lse, float* scores,
-                                       long long score_floats, int B, int T, int H, int HD, float drop_p,
-                                       unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
-                                       void* stream) {
-  const int HDk = fs2hip_attention_padded_dim(HD);
-  if (HDk == 0 || B <= 0 || T <= 0 || H <= 0 || operand_bf16 < 0 || operand_bf16 > 2 || !aligned16(qkv) || !aligned16(o))
+// scores non-null: the forward pass that also writes its masked scores out for the backward pass
+extern "C" int fs2hip_attention_fwd(const float* qkv, const int* lens, float* o, float* lse, float* scores,
+                                    long long score_floats, int B, int T, int H, int HD, float drop_p,
+                                    unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
+                                    void* stream) {
+  if (!attn_args_ok(B, T, H, HD, operand_bf16, scores != nullptr) || !aligned16(qkv) || !aligned16(o) || !aligned16(scores))
     return FS2HIP_EINVAL;
+  const int HDk = fs2hip_attention_padded_dim(HD);
   const float scale = 1.f / sqrtf((float)HD);
   const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
-  if (scores) {
-    if (operand_bf16 == 1 || !aligned16(scores)) return FS2HIP_EINVAL;
+  if (scores)
     return attn_fwd_s_run(qkv, lens, o, lse, scores, score_floats, B, T, H, HDk, scale, drop, operand_bf16,
                           (hipStream_t)stream);
-  }
   return attn_fwd_run(qkv, lens, o, lse, B, T, H, HDk, scale, drop, operand_bf16, (hipStream_t)stream);
 }
 
-extern "C" int fs2hip_attention_bwd_hd(const float* qkv, const int* lens, const float* o, const float* dout,
-                                       const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
-                                       float* dqkv, int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
-                                       const unsigned long long* drop_step, int operand_bf16, void* stream) {
-  const int HDk = fs2hip_attention_padded_dim(HD);
-  if (HDk == 0 || B <= 0 || T <= 0 || H <= 0 || operand_bf16 < 0 || operand_bf16 > 2 || !aligned16(qkv) || !aligned16(o) ||
-      !aligned16(dout) || !aligned16(dqkv))
+// ds non-null: the spilled-dS backward (its dK/dV kernel reads `scores` when given instead of recomputing K.Q^T); ds null:
+// the recomputing backward with aux as its delta scratch
+extern "C" int fs2hip_attention_bwd(const float* qkv, const int* lens, const float* o, const float* dout,
+                                    const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
+                                    float* dqkv, int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
+                                    const unsigned long long* drop_step, int operand_bf16, void* stream) {
+  if (!attn_args_ok(B, T, H, HD, operand_bf16, scores || ds) || (scores && !ds) || !aligned16(qkv) || !aligned16(o) ||
+      !aligned16(dout) || !aligned16(dqkv) || !aligned16(scores) || !aligned16(ds))
     return FS2HIP_EINVAL;
+  const int HDk = fs2hip_attention_padded_dim(HD);
   const float scale = 1.f / sqrtf((float)HD);
   const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
-  if (ds) {  // the spilled-dS backward: exact fp32 or "32-split", whose dK/dV kernel is the fp32 one
-    if (operand_bf16 == 1 || !aligned16(ds) || !aligned16(scores)) return FS2HIP_EINVAL;
+  if (ds)
     return attn_bwd_spill_run(qkv, lens, o, dout, lse, scores, aux, ds, ds_floats, dqkv, B, T, H, HDk, scale, drop,
                               (hipStream_t)stream);
-  }
-  if (scores) return FS2HIP_EINVAL;
   return attn_bwd_run(qkv, lens, o, dout, lse, aux, dqkv, B, T, H, HDk, scale, drop, operand_bf16, (hipStream_t)stream);
 }

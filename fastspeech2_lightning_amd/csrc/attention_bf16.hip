@@ -721,37 +721,30 @@ int fs2_attnb_bwd(const Attn2Args& a, const void* qkv, const void* o, const void
   return 0;
 }
 
+// a required tensor of the bf16-storage entry points: there, and accessed in 16-byte pieces
+static bool attnb_tensor_ok(const void* p) { return p && (uintptr_t)p % 16 == 0; }
+
 extern "C" int fs2hip_attention_fwd_b(const void* qkv, const int* lens, void* o, float* lse, int B, int T, int H, int HD,
                                       float drop_p, unsigned long long drop_seed, const unsigned long long* drop_step,
                                       void* stream) {
-  if (!qkv || !lens || !o || !lse || ((uintptr_t)qkv % 16) || ((uintptr_t)o % 16)) return FS2HIP_EINVAL;
+  if (!lens || !lse || !attnb_tensor_ok(qkv) || !attnb_tensor_ok(o)) return FS2HIP_EINVAL;
   Attn2Args a{nullptr, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step), 1, nullptr};
   return fs2_attnb_fwd(a, qkv, o, lse, (hipStream_t)stream);
 }
 
+// ds non-null: dS -- masked, rounded to bf16 -- is written out by the dK/dV kernel (ds_elems >= B * H * T * (T rounded up to
+// 32) bf16 elements of scratch) and dQ = scale * dS . K is a product of its own: the recomputing dQ kernel's S, dP and
+// softmax / dropout arithmetic are not run a second time.  ds null: both gradient kernels recompute.
 extern "C" int fs2hip_attention_bwd_b(const void* qkv, const int* lens, const void* o, const void* dout, const float* lse,
-                                      float* aux, void* dqkv, int B, int T, int H, int HD, float drop_p,
-                                      unsigned long long drop_seed, const unsigned long long* drop_step, void* stream) {
-  if (!qkv || !lens || !o || !dout || !lse || !aux || !dqkv || ((uintptr_t)qkv % 16) || ((uintptr_t)o % 16) ||
-      ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) || ((uintptr_t)aux % 16))
+                                      float* aux, void* ds, long long ds_elems, void* dqkv, int B, int T, int H, int HD,
+                                      float drop_p, unsigned long long drop_seed, const unsigned long long* drop_step,
+                                      void* stream) {
+  if (!lens || !lse || !attnb_tensor_ok(qkv) || !attnb_tensor_ok(o) || !attnb_tensor_ok(dout) || !attnb_tensor_ok(dqkv) ||
+      !attnb_tensor_ok(aux) || ((uintptr_t)ds % 16))
     return FS2HIP_EINVAL;
-  Attn2Args a{nullptr, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step), 1, nullptr};
-  return fs2_attnb_bwd(a, qkv, o, dout, lse, aux, dqkv, (hipStream_t)stream);
-}
-
-extern "C" int fs2hip_attention_b_supported(int HD) { return fs2_attnb_supported(HD) ? 1 : 0; }
-
-// fs2hip_attention_bwd_b with dS written out by the dK/dV kernel (bf16, B * H * T * (T rounded up to 32) elements of scratch
-// in `ds`) and dQ = scale * dS . K as a product of its own: the recomputing dQ kernel's S, dP and softmax / dropout arithmetic
-// are not run a second time.
-extern "C" int fs2hip_attention_bwd_b_spill(const void* qkv, const int* lens, const void* o, const void* dout, const float* lse,
-                                            float* aux, void* ds, long long ds_elems, void* dqkv, int B, int T, int H, int HD,
-                                            float drop_p, unsigned long long drop_seed, const unsigned long long* drop_step,
-                                            void* stream) {
-  if (!qkv || !lens || !o || !dout || !lse || !aux || !dqkv || !ds || ((uintptr_t)qkv % 16) || ((uintptr_t)o % 16) ||
-      ((uintptr_t)dout % 16) || ((uintptr_t)dqkv % 16) || ((uintptr_t)aux % 16) || ((uintptr_t)ds % 16))
-    return FS2HIP_EINVAL;
-  if (ds_elems < (long long)B * H * T * ((T + 31) & ~31)) return FS2HIP_EINVAL;
+  if (ds && ds_elems < (long long)B * H * T * ((T + 31) & ~31)) return FS2HIP_EINVAL;
   Attn2Args a{nullptr, lens, B, T, H, HD, 1.f / sqrtf((float)HD), fs2_make_drop(drop_p, drop_seed, drop_step), 1, nullptr};
   return fs2_attnb_bwd(a, qkv, o, dout, lse, aux, dqkv, (hipStream_t)stream, ds);
 }
+
+extern "C" int fs2hip_attention_b_supported(int HD) { return fs2_attnb_supported(HD) ? 1 : 0; }

@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
 
 }  // namespace
 
-extern "C" int fs2hip_version(void) { return 1; }
+extern "C" int fs2hip_version(void) { return 2; }  // 2: one attention forward / backward entry point per family
 
 namespace {
 // which launcher takes a prepared GemmP: the bf16-storage core, the direct-to-LDS fp32 cores (tile >= 4), the

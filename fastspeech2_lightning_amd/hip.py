@@ -76,20 +76,14 @@ SIGNATURES = {
     "fs2hip_layernorm_bwd_pred": "ppppppipiifQpp",
     "fs2hip_layernorm_bwd_x": "ppppppppffQppiiip",
     "fs2hip_dwconv_bwd_b": "ppippipppiiiiip",
-    "fs2hip_attention_fwd": "ppppiiiifQpip",
-    "fs2hip_attention_bwd": "pppppppiiiifQpip",
-    "fs2hip_attention_bwd_spill_supported": "i",
-    "fs2hip_attention_bwd_spill": "pppppppqpiiiifQpp",
-    "fs2hip_attention_fwd_s": "pppppqiiiifQpip",
-    "fs2hip_attention_bwd_spill_s": "ppppppppqpiiiifQpp",
     "fs2hip_attention_padded_dim": "i",
     "fs2hip_attention_pad_heads": "ppiiiip",
     "fs2hip_attention_unpad_heads": "ppiiiip",
-    "fs2hip_attention_fwd_hd": "pppppqiiiifQpip",
-    "fs2hip_attention_bwd_hd": "ppppppppqpiiiifQpip",
+    "fs2hip_attention_bwd_spill_supported": "i",
+    "fs2hip_attention_fwd": "pppppqiiiifQpip",
+    "fs2hip_attention_bwd": "ppppppppqpiiiifQpip",
     "fs2hip_attention_fwd_b": "ppppiiiifQpp",
-    "fs2hip_attention_bwd_b": "pppppppiiiifQpp",
-    "fs2hip_attention_bwd_b_spill": "pppppppqpiiiifQpp",
+    "fs2hip_attention_bwd_b": "pppppppqpiiiifQpp",
     "fs2hip_attention_b_supported": "i",
     "fs2hip_dwconv_blocks": "ii",
     "fs2hip_dwconv_part_rows": "",
@@ -1369,8 +1363,6 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dx_add=None, defer=Fa
 ATTN_SCORES = os.environ.get("FS2_ATTN_SCORES", "1") != "0"
 
 
-#: head dims the attention kernels are built for; the others run zero-padded to ``attention_padded_dim``
-ATTN_NATIVE_HD = (16, 32, 64, 128)
 #: the largest head dimension the attention kernels take (padded or not)
 ATTN_MAX_HD = 256
 
@@ -1409,43 +1401,25 @@ def _unpad_heads(xp, out, rows, groups, HDp, HD):
 
 def attention_fwd(qkv, lens, B, T, H, drop: Drop = NO_DROP, save_scores=False):
     """``save_scores`` (training forward): returns (o, lse, scores) -- scores [B, H, T, T rounded up to 32] for the backward
-    pass, or None where ``attention_scores_kept`` says no.  Any head dimension up to 256: 16 / 32 / 64 / 128 run as they
-    are, the others on the zero-padded route (``attention_padded_dim``)."""
+    pass, or None where ``attention_scores_kept`` says no.  Any head dimension up to 256: 16 / 32 / 64 / 128 / 256 run as
+    they are, the others with q | k | v zero-padded to ``attention_padded_dim`` columns per head, the kernels at that width
+    with the softmax scale of HD, and o cut back to HD columns per head."""
     _chk(qkv, name="qkv"); _chk(lens, torch.int32, "lens")
     D = qkv.shape[-1] // 3
     _req(_rows(qkv) == B * T and qkv.shape[-1] == 3 * D and D % H == 0 and lens.numel() == B,
          "attention_fwd: shape mismatch")
     HD = _head_dim(D, H, "attention_fwd")
-    if HD not in ATTN_NATIVE_HD:
-        return _attention_fwd_hd(qkv, lens, B, T, H, HD, drop, save_scores)
-    o = torch.empty(B, T, D, device=qkv.device, dtype=torch.float32)
-    lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
-    if save_scores:
-        if not attention_scores_kept(D // H):
-            o, lse = attention_fwd(qkv, lens, B, T, H, drop)
-            return o, lse, None
-        sc = torch.empty(B, H, T, (T + 31) // 32 * 32, device=qkv.device, dtype=torch.float32)
-        _ok(lib().fs2hip_attention_fwd_s(_p(qkv), _p(lens), _p(o), _p(lse), _p(sc), sc.numel(), B, T, H, D // H, drop.p, drop.seed,
-                                         drop.step_ptr, int(GEMM_BF16), _stream()), "attention_fwd_s")
-        return o, lse, sc
-    _ok(lib().fs2hip_attention_fwd(_p(qkv), _p(lens), _p(o), _p(lse), B, T, H, D // H, drop.p, drop.seed,
-                                   drop.step_ptr, int(GEMM_BF16), _stream()), "attention_fwd")
-    return o, lse
-
-
-def _attention_fwd_hd(qkv, lens, B, T, H, HD, drop, save_scores):
-    """The forward pass at a head dimension the kernels are not built for: q | k | v zero-padded to HDp columns per head
-    (skipped at HDp = HD = 256), the kernels at HDp with the softmax scale of HD, o cut back to HD columns per head."""
-    HDp, D, rows = attention_padded_dim(HD), H * HD, B * T
+    HDp, rows = attention_padded_dim(HD), B * T
     qkvp = qkv if HDp == HD else _pad_heads(qkv, rows, 3 * H, HD, HDp)
-    op = torch.empty(B, T, H * HDp, device=qkv.device, dtype=torch.float32)
+    o = torch.empty(B, T, H * HDp, device=qkv.device, dtype=torch.float32)
     lse = torch.empty(B, H, T, device=qkv.device, dtype=torch.float32)
     sc = None
     if save_scores and attention_scores_kept(HD):
         sc = torch.empty(B, H, T, (T + 31) // 32 * 32, device=qkv.device, dtype=torch.float32)
-    _ok(lib().fs2hip_attention_fwd_hd(_p(qkvp), _p(lens), _p(op), _p(lse), _p(sc), 0 if sc is None else sc.numel(), B, T, H,
-                                      HD, drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()), "attention_fwd_hd")
-    o = op if HDp == HD else _unpad_heads(op, torch.empty(B, T, D, device=qkv.device, dtype=torch.float32), rows, H, HDp, HD)
+    _ok(lib().fs2hip_attention_fwd(_p(qkvp), _p(lens), _p(o), _p(lse), _p(sc), 0 if sc is None else sc.numel(), B, T, H, HD,
+                                   drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()), "attention_fwd")
+    if HDp != HD:
+        o = _unpad_heads(o, torch.empty(B, T, D, device=qkv.device, dtype=torch.float32), rows, H, HDp, HD)
     return (o, lse, sc) if save_scores else (o, lse)
 
 
@@ -1477,6 +1451,8 @@ def release_scratch():
 
 
 def attention_bwd(qkv, lens, o, dout, lse, B, T, H, drop: Drop = NO_DROP, scores=None):
+    """The backward pass of ``attention_fwd``.  At a padded head dimension qkv, o and dout are zero-padded again (o's pad
+    columns are the forward's exact zeros) and dqkv is cut back to HD columns per head."""
     for n, t in (("qkv", qkv), ("o", o), ("dout", dout), ("lse", lse)):
         _chk(t, name=n)
     _chk(lens, torch.int32, "lens")
@@ -1484,56 +1460,30 @@ def attention_bwd(qkv, lens, o, dout, lse, B, T, H, drop: Drop = NO_DROP, scores
     _req(_rows(qkv) == B * T and o.numel() == B * T * D and dout.numel() == B * T * D and lse.numel() == B * H * T
          and lens.numel() == B, "attention_bwd: shape mismatch")
     HD = _head_dim(D, H, "attention_bwd")
-    if HD not in ATTN_NATIVE_HD:
-        return _attention_bwd_hd(qkv, lens, o, dout, lse, B, T, H, HD, drop, scores)
-    dqkv = torch.empty_like(qkv)
-    delta = torch.empty(2 * lse.numel() + 4, device=lse.device, dtype=torch.float32)  # scratch: see fs2hip.h
-    if GEMM_BF16 in (0, 2) and ATTN_SPILL and lib().fs2hip_attention_bwd_spill_supported(D // H):
+    HDp, rows = attention_padded_dim(HD), B * T
+    pad = HDp != HD
+    qkvp = qkv
+    if pad:
+        qkvp = _pad_heads(qkv, rows, 3 * H, HD, HDp)
+        o = _pad_heads(o, rows, H, HD, HDp)
+        dout = _pad_heads(dout, rows, H, HD, HDp)
+    dqkv = torch.empty(rows, 3 * H * HDp, device=qkv.device, dtype=torch.float32) if pad else torch.empty_like(qkv)
+    aux = torch.empty(2 * lse.numel() + 4, device=lse.device, dtype=torch.float32)  # scratch: see fs2hip.h
+    ds, n = None, 0
+    if GEMM_BF16 in (0, 2) and ATTN_SPILL and lib().fs2hip_attention_bwd_spill_supported(HDp):
         # exact fp32 and "32-split" (whose dK/dV kernel is the fp32 one): the dK/dV kernel writes dS out and dQ is a product
         # of its own on the fp32 MFMAs (5 products per block instead of 9)
         n = B * H * T * ((T + 31) // 32 * 32)
-        ds = reserve_scratch("attn_ds", n)
-        if scores is not None:
-            _chk(scores, name="scores")
-            _req(scores.numel() == n, "attention_bwd: scores must be [B, H, T, T rounded up to 32]")
-            _ok(lib().fs2hip_attention_bwd_spill_s(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(scores), _p(delta), _p(ds), n,
-                                                   _p(dqkv), B, T, H, D // H, drop.p, drop.seed, drop.step_ptr, _stream()),
-                "attention_bwd_spill_s")
-            return dqkv
-        _ok(lib().fs2hip_attention_bwd_spill(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(delta), _p(ds), n, _p(dqkv), B, T, H,
-                                             D // H, drop.p, drop.seed, drop.step_ptr, _stream()), "attention_bwd_spill")
-        return dqkv
-    _ok(lib().fs2hip_attention_bwd(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(delta), _p(dqkv), B, T, H, D // H,
-                                   drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()), "attention_bwd")
-    return dqkv
-
-
-def _attention_bwd_hd(qkv, lens, o, dout, lse, B, T, H, HD, drop, scores):
-    """The backward pass of ``_attention_fwd_hd``: qkv, o and dout zero-padded to HDp columns per head (o's pad columns
-    are the forward's exact zeros), the kernels at HDp, dqkv cut back to HD columns per head."""
-    HDp, rows = attention_padded_dim(HD), B * T
-    pad = HDp != HD
-    qkvp = _pad_heads(qkv, rows, 3 * H, HD, HDp) if pad else qkv
-    op = _pad_heads(o, rows, H, HD, HDp) if pad else o
-    doutp = _pad_heads(dout, rows, H, HD, HDp) if pad else dout
-    dqkvp = torch.empty(rows, 3 * H * HDp, device=qkv.device, dtype=torch.float32)
-    aux = torch.empty(2 * lse.numel() + 4, device=lse.device, dtype=torch.float32)
-    ds, n = None, 0
-    if GEMM_BF16 in (0, 2) and ATTN_SPILL and lib().fs2hip_attention_bwd_spill_supported(HDp):
-        # (a step allocation, not reserve_scratch: under a launch plan it lives in the plan's own pool)
-        n = B * H * T * ((T + 31) // 32 * 32)
-        ds = torch.empty(n, device=qkv.device, dtype=torch.float32)
+        # (padded: a step allocation, not reserve_scratch -- under a launch plan it lives in the plan's own pool)
+        ds = torch.empty(n, device=qkv.device, dtype=torch.float32) if pad else reserve_scratch("attn_ds", n)
         if scores is not None:
             _chk(scores, name="scores")
             _req(scores.numel() == n, "attention_bwd: scores must be [B, H, T, T rounded up to 32]")
     else:
-        scores = None
-    _ok(lib().fs2hip_attention_bwd_hd(_p(qkvp), _p(lens), _p(op), _p(doutp), _p(lse), _p(scores), _p(aux), _p(ds), n,
-                                      _p(dqkvp), B, T, H, HD, drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()),
-        "attention_bwd_hd")
-    if not pad:
-        return dqkvp.view_as(qkv)
-    return _unpad_heads(dqkvp, torch.empty_like(qkv), rows, 3 * H, HDp, HD)
+        scores = None  # kept for a backward that does not spill: not read
+    _ok(lib().fs2hip_attention_bwd(_p(qkvp), _p(lens), _p(o), _p(dout), _p(lse), _p(scores), _p(aux), _p(ds), n, _p(dqkv),
+                                   B, T, H, HD, drop.p, drop.seed, drop.step_ptr, int(GEMM_BF16), _stream()), "attention_bwd")
+    return _unpad_heads(dqkv, torch.empty_like(qkv), rows, 3 * H, HDp, HD) if pad else dqkv
 
 
 def attention_b_supported(HD: int) -> bool:
@@ -1570,14 +1520,10 @@ def attention_bwd_b(qkv, lens, o, dout, lse, B, T, H, drop: Drop = NO_DROP):
     _req(attention_b_supported(D // H), "attention_bwd_b: head dimension not supported by the bf16-storage kernels")
     dqkv = torch.empty_like(qkv)
     aux = torch.empty(2 * lse.numel() + 4, device=lse.device, dtype=torch.float32)  # {lse', delta'} per row and head
-    if ATTN_SPILL_B:
-        n = B * H * T * ((T + 31) // 32 * 32)  # bf16 elements
-        ds = reserve_scratch("attnb_ds", (n + 1) // 2)
-        _ok(lib().fs2hip_attention_bwd_b_spill(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(aux), _p(ds), n, _p(dqkv), B, T, H,
-                                               D // H, drop.p, drop.seed, drop.step_ptr, _stream()), "attention_bwd_b_spill")
-        return dqkv
-    _ok(lib().fs2hip_attention_bwd_b(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(aux), _p(dqkv), B, T, H, D // H,
-                                     drop.p, drop.seed, drop.step_ptr, _stream()), "attention_bwd_b")
+    n = B * H * T * ((T + 31) // 32 * 32)  # bf16 elements
+    ds = reserve_scratch("attnb_ds", (n + 1) // 2) if ATTN_SPILL_B else None
+    _ok(lib().fs2hip_attention_bwd_b(_p(qkv), _p(lens), _p(o), _p(dout), _p(lse), _p(aux), _p(ds), 0 if ds is None else n,
+                                     _p(dqkv), B, T, H, D // H, drop.p, drop.seed, drop.step_ptr, _stream()), "attention_bwd_b")
     return dqkv
 
 

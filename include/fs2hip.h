@@ -41,7 +41,7 @@ enum {
   FS2_EPI_DACT = 3   /* C = v * act'(aux) * dropmask   (backward through ACT)         */
 };
 
-int fs2hip_version(void);
+int fs2hip_version(void); /* 2 since attention has one forward and one backward entry point per family */
 
 /* ------------------------------------------------------------------------------------
  * GEMM on fp32 MFMA (v_mfma_f32_32x32x2_f32; bf16 operands on request):  C[Mc][Nc] = epi( sum_r A(m,r) * B(r,n) )
@@ -225,93 +225,66 @@ int fs2hip_layernorm_bwd_x(const void* dy, const float* x, const float* gamma, c
  * head dims 64 / 128 -- attention2.hip -- and 16x16x4 for head dims 16 / 32 / 256).
  * Replaces nn.MultiheadAttention's scaled-dot-product core inside torchaudio's
  * ConformerLayer (call sites fs2/model.py:193, :241).
- *   qkv  [B*T][3*H*HD]  in_proj output (q | k | v);  lens [B] int32 (keys >= lens[b] masked)
- *   o    [B*T][H*HD];   lse [B][H][T] (log-sum-exp per query, saved for the backward)
- *   dropout acts on the normalised probabilities (attention dropout), mask regenerated
- *   from (seed, b, h, q, k) in the backward.  HD in {16, 32, 64, 128} (other head dims: the _hd entry points below).
- * bwd: delta = scratch of 2*B*H*T + 4 floats ({lse', delta'} pairs per row and head); dqkv [B*T][3*H*HD]
- *      fully written.
- * operand_bf16 = 1 ("bf16-mixed"): the operands of all five products (Q, K, V, dO, P, dS) are rounded to bf16 for
- *   v_mfma_f32_16x16x32_bf16; scores, softmax statistics, accumulators and outputs stay fp32.
- * ------------------------------------------------------------------------------------ */
-int fs2hip_attention_fwd(const float* qkv, const int* lens, float* o, float* lse, int B, int T, int H,
-                         int HD, float drop_p, unsigned long long drop_seed,
-                         const unsigned long long* drop_step, int operand_bf16, void* stream);
-int fs2hip_attention_bwd(const float* qkv, const int* lens, const float* o, const float* dout,
-                         const float* lse, float* delta, float* dqkv, int B, int T, int H, int HD,
-                         float drop_p, unsigned long long drop_seed,
-                         const unsigned long long* drop_step, int operand_bf16, void* stream);
-
-/* The fp32 backward pass (operand_bf16 = 0) with dS written out by the dK/dV kernel and dQ = scale * dS . K as a product
- * of its own -- 5 products per block instead of the 9 of two kernels that each recompute S and dP.
- * Head dims for which fs2hip_attention_bwd_spill_supported() returns 1 (64, 128).
- *   aux: 2*B*H*T + 4 floats; ds: scratch of at least B*H*T*(T rounded up to 32) floats (ds_floats = its size).
- * Same results as fs2hip_attention_bwd up to the rounding of S (the scale is folded into K there, into Q in the
- * recomputing dQ kernel). */
-int fs2hip_attention_bwd_spill_supported(int HD);
-int fs2hip_attention_bwd_spill(const float* qkv, const int* lens, const float* o, const float* dout,
-                               const float* lse, float* aux, float* ds, long long ds_floats, float* dqkv,
-                               int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
-                               const unsigned long long* drop_step, void* stream);
-
-/* ... and with the forward pass's masked scores kept for it: fs2hip_attention_fwd_s writes them (log2 units, scale folded
- * in, -inf at masked keys) into `scores` (at least B*H*T*(T rounded up to 32) floats, kept until the backward pass), and
- * fs2hip_attention_bwd_spill_s's dK/dV kernel reads them instead of recomputing K.Q^T: 3 + 1 products per block in the
- * backward pass, and the backward's probabilities are the forward's to the bit.  operand_bf16: 0 (exact fp32) or 2
- * ("32-split": the scores come from the three-plane products; the backward pass is the fp32 one either way). */
-int fs2hip_attention_fwd_s(const float* qkv, const int* lens, float* o, float* lse, float* scores,
-                           long long score_floats, int B, int T, int H, int HD, float drop_p,
-                           unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
-                           void* stream);
-int fs2hip_attention_bwd_spill_s(const float* qkv, const int* lens, const float* o, const float* dout,
-                                 const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
-                                 float* dqkv, int B, int T, int H, int HD, float drop_p,
-                                 unsigned long long drop_seed, const unsigned long long* drop_step, void* stream);
-
-/* Any head dimension 1 <= HD <= 256.  The kernels run at the padded width HDp = fs2hip_attention_padded_dim(HD) (the
- * smallest of 16, 32, 64, 128, 256 that holds HD; 0: refused) with the softmax scale 1/sqrt(HD) of the TRUE head dimension.
+ *
+ * Any head dimension 1 <= HD <= 256.  The tensors are laid out, and the kernels run, at the padded width
+ * HDp = fs2hip_attention_padded_dim(HD): the smallest of 16, 32, 64, 128, 256 that holds HD (0: refused) -- HD itself at
+ * those five; the softmax scale is 1/sqrt(HD) of the TRUE head dimension.
+ *   qkv  [B*T][3*H*HDp]  in_proj output (q | k | v);  lens [B] int32 (keys >= lens[b] masked)
+ *   o, dout [B*T][H*HDp];  lse [B][H][T] (log-sum-exp per query, saved for the backward);  dqkv [B*T][3*H*HDp], fully written
+ *   dropout acts on the normalised probabilities (attention dropout), mask regenerated from (seed, b, h, q, k) in the
+ *   backward: it does not depend on the head width.
  * fs2hip_attention_pad_heads: [rows][groups*HD] -> [rows][groups*HDp], the pad columns written as zeros (qkv: groups = 3H;
- *   dout and o: groups = H).  fs2hip_attention_unpad_heads: [rows][groups*HDp] -> [rows][groups*HD] (o, dqkv).
- * fs2hip_attention_fwd_hd / _bwd_hd: the operations above on the padded tensors (qkv [B*T][3*H*HDp], o / dout
- *   [B*T][H*HDp], dqkv [B*T][3*H*HDp]; at HD = HDp the unpadded ones).  Zero columns of Q and K add exact zeros to every
- *   score and zero columns of V give zero output columns, so the results are those of the true head dimension; the
- *   dropout mask is that of fs2hip_attention_fwd (it depends on b, h, q, key only).
- *   fwd_hd: scores non-null = fs2hip_attention_fwd_s (operand_bf16 0 or 2, HDp 64 / 128).
- *   bwd_hd: ds non-null = the spilled-dS backward (fs2hip_attention_bwd_spill, _s when scores is non-null; operand_bf16
- *   0 or 2, HDp 64 / 128); ds null = fs2hip_attention_bwd with aux as its delta scratch. */
+ *   dout and o: groups = H).  fs2hip_attention_unpad_heads: [rows][groups*HDp] -> [rows][groups*HD] (o, dqkv).  Zero columns
+ *   of Q and K add exact zeros to every score and zero columns of V give zero output columns, so the results on the padded
+ *   tensors are those of the true head dimension.
+ * operand_bf16 = 1 ("bf16-mixed"): the operands of all five products (Q, K, V, dO, P, dS) are rounded to bf16 for
+ *   v_mfma_f32_16x16x32_bf16; scores, softmax statistics, accumulators and outputs stay fp32.  2 ("32-split"): three exact
+ *   bf16 planes for the forward and dQ products.
+ * fwd:
+ *   scores (optional): when non-null the masked scores (log2 units, scale folded in, -inf at masked keys) are also written
+ *     there, kept by the caller until the backward pass.  At least B*H*T*(T rounded up to 32) floats (score_floats = its
+ *     size); operand_bf16 0 or 2, HDp 64 / 128.
+ * bwd:
+ *   aux: scratch of 2*B*H*T + 4 floats ({lse', delta'} pairs per row and head).
+ *   ds (optional): non-null selects the backward with dS written out by the dK/dV kernel and dQ = scale * dS . K as a
+ *     product of its own -- 5 products per block instead of the 9 of two kernels that each recompute S and dP (DESIGN.md
+ *     section 4a).  Scratch of at least B*H*T*(T rounded up to 32) floats (ds_floats = its size); operand_bf16 0 or 2
+ *     (the dK/dV kernel is the fp32 one either way), HDp for which fs2hip_attention_bwd_spill_supported() returns 1
+ *     (64, 128).  Same results as with ds null up to the rounding of S (the scale is folded into K there, into Q in the
+ *     recomputing dQ kernel).
+ *   scores (optional, only with ds): the forward pass's; the dK/dV kernel reads them instead of recomputing K.Q^T -- 3 + 1
+ *     products per block, and the backward's probabilities are the forward's to the bit.
+ * ------------------------------------------------------------------------------------ */
 int fs2hip_attention_padded_dim(int HD);
 int fs2hip_attention_pad_heads(const float* src, float* dst, int rows, int groups, int HD, int HDp, void* stream);
 int fs2hip_attention_unpad_heads(const float* src, float* dst, int rows, int groups, int HDp, int HD, void* stream);
-int fs2hip_attention_fwd_hd(const float* qkv, const int* lens, float* o, float* lse, float* scores,
-                            long long score_floats, int B, int T, int H, int HD, float drop_p,
-                            unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
-                            void* stream);
-int fs2hip_attention_bwd_hd(const float* qkv, const int* lens, const float* o, const float* dout,
-                            const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
-                            float* dqkv, int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
-                            const unsigned long long* drop_step, int operand_bf16, void* stream);
+int fs2hip_attention_bwd_spill_supported(int HD);
+int fs2hip_attention_fwd(const float* qkv, const int* lens, float* o, float* lse, float* scores,
+                         long long score_floats, int B, int T, int H, int HD, float drop_p,
+                         unsigned long long drop_seed, const unsigned long long* drop_step, int operand_bf16,
+                         void* stream);
+int fs2hip_attention_bwd(const float* qkv, const int* lens, const float* o, const float* dout,
+                         const float* lse, const float* scores, float* aux, float* ds, long long ds_floats,
+                         float* dqkv, int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
+                         const unsigned long long* drop_step, int operand_bf16, void* stream);
 
 /* The same attention on tensors that ARE bf16 in memory (precision "bf16-mixed" with bf16 activation
  * storage; torch.autocast(bfloat16) around nn.MultiheadAttention, call sites fs2/model.py:193, :241):
  * qkv, o, dout, dqkv are bf16 with the shapes above, lse and the scratch `aux` (2*B*H*T + 4 floats)
  * are fp32.  Head dims for which fs2hip_attention_b_supported() returns 1 (128).  The dropout keep
- * mask is the one fs2hip_attention_fwd generates for the same (drop_p, drop_seed, drop_step). */
+ * mask is the one fs2hip_attention_fwd generates for the same (drop_p, drop_seed, drop_step).
+ *   ds (optional): non-null selects the backward with dS -- masked and rounded to bf16: the operand the dQ product
+ *     consumes -- written out by the dK/dV kernel and dQ = scale * dS . K as a product of its own: S, dP and the softmax /
+ *     dropout arithmetic are computed once per backward pass instead of twice.  Scratch of at least B*H*T*(T rounded up
+ *     to 32) bf16 elements (ds_elems = its size, read only when ds is non-null). */
 int fs2hip_attention_b_supported(int HD);
 int fs2hip_attention_fwd_b(const void* qkv, const int* lens, void* o, float* lse, int B, int T, int H,
                            int HD, float drop_p, unsigned long long drop_seed,
                            const unsigned long long* drop_step, void* stream);
 int fs2hip_attention_bwd_b(const void* qkv, const int* lens, const void* o, const void* dout,
-                           const float* lse, float* aux, void* dqkv, int B, int T, int H, int HD,
-                           float drop_p, unsigned long long drop_seed,
+                           const float* lse, float* aux, void* ds, long long ds_elems, void* dqkv,
+                           int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
                            const unsigned long long* drop_step, void* stream);
-
-/* fs2hip_attention_bwd_b with dS -- masked and rounded to bf16: the operand the dQ product consumes -- written out by the
- * dK/dV kernel and dQ = scale * dS . K as a product of its own: S, dP and the softmax / dropout arithmetic are computed once
- * per backward pass instead of twice.  ds: scratch of at least B*H*T*(T rounded up to 32) bf16 elements (ds_elems). */
-int fs2hip_attention_bwd_b_spill(const void* qkv, const int* lens, const void* o, const void* dout,
-                                 const float* lse, float* aux, void* ds, long long ds_elems, void* dqkv,
-                                 int B, int T, int H, int HD, float drop_p, unsigned long long drop_seed,
-                                 const unsigned long long* drop_step, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Depthwise Conv1d over time on (B, T, C), 'same' padding, K in {3,5,7,9,15,31}; w is [K][C].

@@ -115,7 +115,7 @@ def test_attention_bf16_storage_rejects_other_head_dims(H):
 
 @pytest.mark.parametrize("B,T,lens", CASES + [(3, 1291, [1291, 700, 64])])
 def test_bf16_storage_backward_with_spilled_ds_equals_the_recomputing_one(H, B, T, lens, monkeypatch):
-    """``fs2hip_attention_bwd_b_spill`` (default): the dK/dV kernel writes dS -- masked, rounded to bf16: the operand the dQ
+    """``fs2hip_attention_bwd_b`` with ``ds`` (default): the dK/dV kernel writes dS -- masked, rounded to bf16: the operand the dQ
     product consumes -- and dQ = scale * dS . K is a product of its own.  dK and dV are the recomputing kernels' bit for bit
     (same kernel, sixteen stores more per block); dQ within bf16 rounding of theirs -- dropout on and off, ragged lengths,
     utterances that end inside a key block, T not a multiple of the tile, T = 1."""

@@ -169,7 +169,7 @@ def test_attention_plane_modes_share_the_dropout_mask(H, precision, tol, T, hd):
     (3, 1291, 2, 128, [1291, 700, 64]),  # BASELINE configs[4]'s longest utterance: 41 key tiles, a 6.8 MB dS slab per head
 ])
 def test_spilled_ds_backward_equals_the_recomputing_backward(H, B, T, Hh, hd, lens, monkeypatch):
-    """``fs2hip_attention_bwd_spill`` (default in "32-true"): the dK/dV kernel writes dS out, dQ = scale * dS . K is its own
+    """``fs2hip_attention_bwd`` with ``ds`` (default in "32-true"): the dK/dV kernel writes dS out, dQ = scale * dS . K is its own
     product.  dK and dV are the recomputing kernels' bit for bit (same kernel, one store more); dQ differs only by the rounding
     of S (scale folded into K instead of Q): 2e-5 of its scale -- with attention dropout on, ragged lengths, T not a multiple of
     the tile, utterances shorter than one key tile."""

@@ -186,13 +186,13 @@ def test_padding_is_invisible_with_dropout(H, kept):
     assert float((o - o0).abs().max()) > 1e-3
 
 
-PAD_ENTRY_POINTS = ("fs2hip_attention_pad_heads", "fs2hip_attention_unpad_heads", "fs2hip_attention_fwd_hd",
-                    "fs2hip_attention_bwd_hd")
+PAD_ENTRY_POINTS = ("fs2hip_attention_pad_heads", "fs2hip_attention_unpad_heads")
 
 
 @pytest.mark.parametrize("hd", [16, 32, 64, 128])
 def test_built_head_dims_keep_their_route(H, monkeypatch, hd):
-    """Head dims 16 / 32 / 64 / 128 call none of the padded route's entry points (they raise here if called)."""
+    """Head dims 16 / 32 / 64 / 128 launch no pad or unpad kernel (those entry points raise here if called), with and
+    without kept scores, and the returned o and dqkv are the very tensors the kernels wrote: no copy."""
     L = H.lib()
 
     def refuse(*a, **k):
@@ -200,12 +200,22 @@ def test_built_head_dims_keep_their_route(H, monkeypatch, hd):
 
     for name in PAD_ENTRY_POINTS:
         monkeypatch.setattr(L, name, refuse)
+    written = {}
+    for name, out in (("fs2hip_attention_fwd", 2), ("fs2hip_attention_bwd", 9)):  # the positions of o and dqkv
+        def spy(*a, _real=getattr(L, name), _name=name, _out=out):
+            written[_name] = a[_out]
+            return _real(*a)
+        monkeypatch.setattr(L, name, spy)
     B, T, Hh, lens = 2, 37, 2, [37, 5]
     qkv, dout, lens_t = (t.cuda() for t in inputs(B, T, Hh * hd, lens, seed=hd))
-    o, lse = H.attention_fwd(qkv, lens_t, B, T, Hh)
-    H.attention_bwd(qkv, lens_t, o, dout, lse, B, T, Hh)
-    o, lse, sc = H.attention_fwd(qkv, lens_t, B, T, Hh, save_scores=True)
-    H.attention_bwd(qkv, lens_t, o, dout, lse, B, T, Hh, scores=sc)
+    for kept in (False, True):
+        if kept:
+            o, lse, sc = H.attention_fwd(qkv, lens_t, B, T, Hh, save_scores=True)
+        else:
+            (o, lse), sc = H.attention_fwd(qkv, lens_t, B, T, Hh), None
+        assert o.shape == (B, T, Hh * hd) and o.data_ptr() == written["fs2hip_attention_fwd"]
+        dqkv = H.attention_bwd(qkv, lens_t, o, dout, lse, B, T, Hh, scores=sc)
+        assert dqkv.shape == qkv.shape and dqkv.data_ptr() == written["fs2hip_attention_bwd"]
 
 
 def test_refusals(H):
@@ -224,3 +234,26 @@ def test_refusals(H):
     qkv_b = torch.randn(B * T, 3 * 2 * 96).cuda().bfloat16()
     with pytest.raises(ValueError, match="head dimension"):
         H.attention_fwd_b(qkv_b, lens, B, T, 2)
+    # the argument contract of the library's own entry points (include/fs2hip.h): each of these returns before any launch
+    L, EINVAL, Tp = H.lib(), -22, 32
+
+    held = []
+
+    def buf(n, dtype=torch.float32):
+        held.append(torch.zeros(n, dtype=dtype, device="cuda"))
+        return held[-1].data_ptr()
+
+    lens_p, lse_p, aux, sc, ds = lens.data_ptr(), lse.data_ptr(), buf(2 * T + 4), buf(T * Tp), buf(T * Tp)
+    qkv_p, o_p, dqkv_p = buf(T * 3 * 64), buf(T * 64), buf(T * 3 * 64)
+    # kept scores with bf16 operands
+    assert L.fs2hip_attention_fwd(qkv_p, lens_p, o_p, lse_p, sc, T * Tp, B, T, Hh, 64, 0.0, 0, None, 1, None) == EINVAL
+    # scores for a backward that does not spill
+    assert L.fs2hip_attention_bwd(qkv_p, lens_p, o_p, o_p, lse_p, sc, aux, None, 0, dqkv_p, B, T, Hh, 64, 0.0, 0, None, 0,
+                                  None) == EINVAL
+    # spilled dS at a width without it
+    assert L.fs2hip_attention_bwd(qkv_p, lens_p, o_p, o_p, lse_p, None, aux, ds, T * Tp, dqkv_p, B, T, Hh, 16, 0.0, 0, None, 0,
+                                  None) == EINVAL
+    # a bf16 dS scratch one element short
+    qkv_b, o_b, dqkv_b, ds_b = (buf(n, torch.bfloat16) for n in (T * 3 * 128, T * 128, T * 3 * 128, T * Tp))
+    assert L.fs2hip_attention_bwd_b(qkv_b, lens_p, o_b, o_b, lse_p, aux, ds_b, T * Tp - 1, dqkv_b, B, T, Hh, 128, 0.0, 0, None,
+                                    None) == EINVAL
