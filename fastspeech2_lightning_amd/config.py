@@ -17,6 +17,7 @@ from enum import Enum
 from pathlib import Path
 from typing import Any, Optional, Union
 
+import torch
 import yaml
 from pydantic import BaseModel, ConfigDict, Field, model_validator
 
@@ -261,10 +262,14 @@ def _load_json_or_yaml(path: Path) -> dict:
 
 
 class InferenceControl(BaseModel):  # reference fs2/type_definitions_heavy.py:15-20
+    """Each control is a float, or a tensor that scales per utterance or per token (the reference multiplies by
+    plain broadcasting, fs2/variance_adaptor.py:203, :360-366): 0-d, [B] / [B, 1], or [B, T] with T the length of that
+    predictor's sequence -- tokens for the duration and for phone-level pitch / energy, frames for frame-level ones,
+    which also take a per-token [B, Ts] tensor (every frame uses its source token's value)."""
     model_config = ConfigDict(arbitrary_types_allowed=True)
-    pitch: float = 1.0
-    energy: float = 1.0
-    duration: float = 1.0
+    pitch: Union[float, torch.Tensor] = 1.0
+    energy: Union[float, torch.Tensor] = 1.0
+    duration: Union[float, torch.Tensor] = 1.0
 
 
 class StatsInfo(BaseModel):  # :23-29

@@ -84,6 +84,48 @@ __global__ __launch_bounds__(256) void bucket_embed_add_kernel(const float* __re
   }
 }
 
+// The same with the control read from device memory (per-token / per-utterance inference control,
+// fs2/variance_adaptor.py:203 with a tensor in InferenceControl).  The control of row r is ctl[r / ctl_div], or, with
+// ctl_idx (the LengthRegulator's src_idx: source token or -1), ctl[(r / ctl_div) * ctl_T + ctl_idx[r]] -- a phone-level
+// [B][ctl_T] control driving a frame-level predictor of ctl_div frames per utterance -- and exactly 1 where ctl_idx[r]
+// lies outside [0, ctl_T).  The row is made wave-uniform, so value, control and the edge search are uniform loads: one
+// read per row.  scaled (optional) receives val * control, the prediction the module returns.
+__global__ __launch_bounds__(256) void bucket_embed_add_ctl_kernel(const float* __restrict__ val,
+                                                                    const float* __restrict__ ctl, int ctl_div,
+                                                                    const int* __restrict__ ctl_idx, int ctl_T,
+                                                                    const float* __restrict__ bins, int NB,
+                                                                    const float* __restrict__ W, const float* __restrict__ x,
+                                                                    float* __restrict__ out, int* __restrict__ idx_out,
+                                                                    float* __restrict__ scaled, int M, int D) {
+  const int row = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  if (row >= M) return;
+  const int grp = row / ctl_div;
+  float c;
+  if (ctl_idx) {
+    const int j = ctl_idx[row];
+    c = (j >= 0 && j < ctl_T) ? ctl[(long long)grp * ctl_T + j] : 1.0f;
+  } else {
+    c = ctl[grp];
+  }
+  const float v = val[row] * c;
+  int lo = 0, hi = NB;  // lower_bound: number of edges strictly below v
+  while (lo < hi) {
+    int mid = (lo + hi) >> 1;
+    if (bins[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  if (lane == 0) {
+    if (idx_out) idx_out[row] = lo;
+    if (scaled) scaled[row] = v;
+  }
+  const float4* e = reinterpret_cast<const float4*>(W + (long long)lo * D);
+  const float4* xi = reinterpret_cast<const float4*>(x + (long long)row * D);
+  float4* o = reinterpret_cast<float4*>(out + (long long)row * D);
+  for (int i = lane; i < (D >> 2); i += 64) {
+    float4 a = xi[i], b = e[i];
+    o[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // LengthRegulator  fs2/variance_adaptor.py:65-81
 // ---------------------------------------------------------------------------------------------
@@ -378,6 +420,16 @@ __global__ void duration_round_kernel(const float* __restrict__ logd, float cont
   out[i] = (int)fmaxf(v, 0.f);
 }
 
+// the same with a control per element group: out[i] uses ctl[i / ctl_div] (same operation order)
+__global__ void duration_round_ctl_kernel(const float* __restrict__ logd, const float* __restrict__ ctl, int ctl_div,
+                                          int* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float e = (float)exp((double)logd[i]);
+  const float v = rintf(e - 1.f) * ctl[i / ctl_div];
+  out[i] = (int)fmaxf(v, 0.f);
+}
+
 inline unsigned grid_for(long long n, int per_block = 256, long long cap = 4096) {
   long long b = (n + per_block - 1) / per_block;
   if (b > cap) b = cap;
@@ -422,6 +474,17 @@ extern "C" int fs2hip_bucket_embed_add(const float* val, float control, const fl
                                        const float* x, float* out, int* idx_out, int M, int D, void* stream) {
   if (M <= 0 || NB <= 0 || D <= 0 || (D % 4)) return FS2HIP_EINVAL;
   bucket_embed_add_kernel<<<dim3((M + 3) / 4), dim3(256), 0, S_>>>(val, control, bins, NB, W, x, out, idx_out, M, D);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_bucket_embed_add_ctl(const float* val, const float* ctl, int ctl_div, const int* ctl_idx, int ctl_T,
+                                           const float* bins, int NB, const float* W, const float* x, float* out,
+                                           int* idx_out, float* scaled, int M, int D, void* stream) {
+  if (M <= 0 || NB <= 0 || D <= 0 || (D % 4)) return FS2HIP_EINVAL;
+  if (!ctl || ctl_div <= 0 || (M % ctl_div) || (ctl_idx && ctl_T <= 0)) return FS2HIP_EINVAL;
+  bucket_embed_add_ctl_kernel<<<dim3((M + 3) / 4), dim3(256), 0, S_>>>(val, ctl, ctl_div, ctl_idx, ctl_T, bins, NB, W, x,
+                                                                       out, idx_out, scaled, M, D);
   FS2_LAUNCH_CHECK();
   return 0;
 }
@@ -558,6 +621,13 @@ extern "C" int fs2hip_sum_slots(const float* x, int n, float* out, void* stream)
 extern "C" int fs2hip_duration_round(const float* logd, float control, int* out, int n, void* stream) {
   if (n <= 0) return FS2HIP_EINVAL;
   duration_round_kernel<<<dim3((n + 255) / 256), dim3(256), 0, S_>>>(logd, control, out, n);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_duration_round_ctl(const float* logd, const float* ctl, int ctl_div, int* out, int n, void* stream) {
+  if (n <= 0 || !ctl || ctl_div <= 0 || (n % ctl_div)) return FS2HIP_EINVAL;
+  duration_round_ctl_kernel<<<dim3((n + 255) / 256), dim3(256), 0, S_>>>(logd, ctl, ctl_div, out, n);
   FS2_LAUNCH_CHECK();
   return 0;
 }

@@ -104,6 +104,7 @@ SIGNATURES = {
     "fs2hip_embedding_fwd": "pppiiip",
     "fs2hip_onehot": "ppiiip",
     "fs2hip_bucket_embed_add": "pfpippppiip",
+    "fs2hip_bucket_embed_add_ctl": "ppipipipppppiip",
     "fs2hip_length_regulate_fwd": "pppppppiiiip",
     "fs2hip_length_regulate_bwd": "pppiiiip",
     "fs2hip_duration_cumsum": "ppppppiiip",
@@ -124,6 +125,7 @@ SIGNATURES = {
     "fs2hip_dact_mul": "pppqip",
     "fs2hip_mask_from_lens": "ppiip",
     "fs2hip_duration_round": "pfpip",
+    "fs2hip_duration_round_ctl": "ppipip",
     "fs2hip_sum_slots": "pipp",
     "fs2hip_attn_dist": "pppiiiip",
     "fs2hip_attn_softmax": "pppppiiip",
@@ -1717,23 +1719,52 @@ def embedding_bwd(idx, dy, dW, padding_idx=-1):
     return linear_bwd_weight(oh, dy, dW, n_valid=V)
 
 
-def bucket_embed_add(val, bins, W, x, control=1.0):
-    """x + W[bucketize(val * control, bins)] ; returns (out, idx int32)."""
+def _ctl_div(control, B, T, what):
+    """Rows per control value of a tensor control over [B, T] rows: one value, one per utterance, or one per row."""
+    _chk(control, name=f"{what}: control")
+    n = control.numel()
+    _req(n in (1, B, B * T), f"{what}: a tensor control holds 1, B or B * T values ({B}, {T}), got {tuple(control.shape)}")
+    return B * T // n
+
+
+def bucket_embed_add(val, bins, W, x, control=1.0, ctl_idx=None, scaled=False):
+    """x + W[bucketize(val * control, bins)] ; returns (out, idx int32).  ``control``: a Python float (a kernel argument),
+    or an fp32 tensor in GPU memory, never read on the host: 1, B or B * T values for ``val`` [B, T]; with ``ctl_idx``
+    (int32 [B, T]: the length regulator's source token per frame or -1) a [B, Ts] tensor whose value for frame (b, t)
+    is ``control[b, ctl_idx[b, t]]`` (1 where the index is -1).  ``scaled=True`` (tensor controls) also returns
+    ``val * control``: (out, idx, scaled)."""
     _chk(val, name="val"); _chk(bins, name="bins"); _chk(W, name="W"); _chk(x, name="x")
     M, D = _rows(x), x.shape[-1]
     _req(val.numel() == M and W.shape[1] == D and W.shape[0] >= bins.numel() + 1, "bucket_embed_add: shape mismatch")
     out = torch.empty_like(x)
     idx = torch.empty(val.shape, device=x.device, dtype=torch.int32)
-    _ok(lib().fs2hip_bucket_embed_add(_p(val), control, _p(bins), bins.numel(), _p(W), _p(x), _p(out), _p(idx), M, D,
-                                      _stream()), "bucket_embed_add")
-    return out, idx
+    if not isinstance(control, torch.Tensor):
+        _req(ctl_idx is None and not scaled, "bucket_embed_add: ctl_idx / scaled go with a tensor control")
+        _ok(lib().fs2hip_bucket_embed_add(_p(val), control, _p(bins), bins.numel(), _p(W), _p(x), _p(out), _p(idx), M, D,
+                                          _stream()), "bucket_embed_add")
+        return out, idx
+    _req(val.dim() == 2, "bucket_embed_add: a tensor control needs val as [B, T]")
+    B, T = val.shape
+    ctl_T = 0
+    if ctl_idx is not None:
+        _chk(control, name="bucket_embed_add: control"); _chk(ctl_idx, torch.int32, "ctl_idx")
+        _req(ctl_idx.shape == val.shape and control.dim() == 2 and control.shape[0] == B,
+             "bucket_embed_add: ctl_idx is [B, T] and its control [B, Ts]")
+        div, ctl_T = T, control.shape[1]
+    else:
+        div = _ctl_div(control, B, T, "bucket_embed_add")
+    sc = torch.empty(val.shape, device=x.device, dtype=torch.float32) if scaled else None
+    _ok(lib().fs2hip_bucket_embed_add_ctl(_p(val), _p(control), div, _p(ctl_idx), ctl_T, _p(bins), bins.numel(), _p(W),
+                                          _p(x), _p(out), _p(idx), _p(sc), M, D, _stream()), "bucket_embed_add_ctl")
+    return (out, idx, sc) if scaled else (out, idx)
 
 
 # ------------------------------------------------------------------------------------------
 # LengthRegulator, predictor head, losses
 # ------------------------------------------------------------------------------------------
-def length_regulate_fwd(x, dur, Tm, table=None):
-    """x [B, Ts, D], dur [B, Ts] int32 -> (out [B, Tm, D], cum, out_lens [B] int32)."""
+def length_regulate_fwd(x, dur, Tm, table=None, want_src_idx=False):
+    """x [B, Ts, D], dur [B, Ts] int32 -> (out [B, Tm, D], cum, out_lens [B] int32); ``want_src_idx``: and the source
+    token of every frame (int32 [B, Tm], -1 past the utterance's end)."""
     _chk(x, name="x"); _chk(dur, torch.int32, "dur")
     B, Ts, D = x.shape
     _req(dur.shape == (B, Ts) and Tm > 0, "length_regulate_fwd: shape mismatch")
@@ -1743,9 +1774,10 @@ def length_regulate_fwd(x, dur, Tm, table=None):
     out = torch.empty(B, Tm, D, device=x.device, dtype=torch.float32)
     cum = torch.empty(B, Ts, device=x.device, dtype=torch.int32)
     lens = torch.empty(B, device=x.device, dtype=torch.int32)
-    _ok(lib().fs2hip_length_regulate_fwd(_p(x), _p(dur), _p(table), _p(out), _p(cum), _p(lens), None, B, Ts, Tm, D,
+    src = torch.empty(B, Tm, device=x.device, dtype=torch.int32) if want_src_idx else None
+    _ok(lib().fs2hip_length_regulate_fwd(_p(x), _p(dur), _p(table), _p(out), _p(cum), _p(lens), _p(src), B, Ts, Tm, D,
                                          _stream()), "length_regulate_fwd")
-    return out, cum, lens
+    return (out, cum, lens, src) if want_src_idx else (out, cum, lens)
 
 
 def length_regulate_bwd(dy, cum):
@@ -2108,9 +2140,16 @@ def attn_dist_bwd(dlogits, q, k, want_dq=True, want_dk=True):
 
 
 def duration_round(logd, control=1.0):
-    """Inference durations: int(max(round_half_even(exp(logd) - 1) * control, 0))."""
+    """Inference durations: int(max(round_half_even(exp(logd) - 1) * control, 0)).  ``control``: a Python float, or an
+    fp32 tensor in GPU memory (never read on the host) of 1, B or B * T values for ``logd`` [B, T]."""
     _chk(logd, name="logd")
     out = torch.empty(logd.shape, device=logd.device, dtype=torch.int32)
+    if isinstance(control, torch.Tensor):
+        _req(logd.dim() == 2, "duration_round: a tensor control needs logd as [B, T]")
+        div = _ctl_div(control, logd.shape[0], logd.shape[1], "duration_round")
+        _ok(lib().fs2hip_duration_round_ctl(_p(logd), _p(control), div, _p(out), logd.numel(), _stream()),
+            "duration_round_ctl")
+        return out
     _ok(lib().fs2hip_duration_round(_p(logd), float(control), _p(out), logd.numel(), _stream()), "duration_round")
     return out
 

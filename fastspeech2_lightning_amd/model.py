@@ -110,7 +110,30 @@ class VarianceAdaptor:
             out.append(names)
         return out
 
-    def _variance(self, name, x, target, lens, control, inference, jobs=None):
+    @staticmethod
+    def _check_control(name, shape, B, T, Ts=None):
+        """The shapes a tensor control may have for a predictor over [B, T] rows: one value, [B] / [B, 1], [B, T], and
+        for a frame-level predictor (``Ts`` given) [B, Ts] as well.  ``T`` None: a frame count not known yet."""
+        shape = tuple(shape)
+        n = 1
+        for d in shape:
+            n *= d
+        if n == 1 or shape == (B,) or (len(shape) == 2 and shape[0] == B and (T is None or shape[1] in (1, T, Ts))):
+            return
+        accepted = f"a float, a 0-d tensor, [B] = [{B}], [B, 1] = [{B}, 1], [B, T] = [{B}, {'frames' if T is None else T}]"
+        if Ts is not None:
+            accepted += f", [B, Ts] = [{B}, {Ts}]"
+        raise ValueError(f"InferenceControl.{name}: got a tensor of shape {list(shape)}; accepted: {accepted}")
+
+    def _control(self, name, value, B, T, Ts=None):
+        """One ``InferenceControl`` field as the kernels take it: a float stays a float (a kernel argument); a tensor is
+        checked (``_check_control``), moved to the GPU as contiguous fp32 once and never read on the host."""
+        if not isinstance(value, torch.Tensor):
+            return value
+        self._check_control(name, value.shape, B, T, Ts)
+        return value.detach().to(device=self.S.flat.device, dtype=torch.float32).contiguous()
+
+    def _variance(self, name, x, target, lens, control, inference, jobs=None, src_idx=None, Ts=None):
         S, pre = self.S, self.pre
         predictor = getattr(self, f"{name}_predictor")
         if inference:
@@ -121,12 +144,20 @@ class VarianceAdaptor:
         else:  # training: the prediction feeds only the loss (the embedding uses the target) -> side stream
             with self.env.side(x, lens, lane=PRED_LANES[name]):
                 pred, pctx = predictor.fwd(x, lens)
-        if inference:
-            out, idx = H.bucket_embed_add(pred, S.b(pre + f"{name}_bins"), S.p(pre + f"{name}_embedding.weight"), x, control)
+        bins, W = S.b(pre + f"{name}_bins"), S.p(pre + f"{name}_embedding.weight")
+        if inference and isinstance(control, torch.Tensor):
+            # per-utterance / per-token control: read by the kernel, which also writes the scaled prediction
+            B, T = pred.shape
+            self._check_control(name, control.shape, B, T, Ts)  # (a frame-level predictor's T: known only now)
+            per_token = control.dim() == 2 and control.shape[1] not in (1, T)  # [B, Ts] for a frame-level predictor
+            out, idx, pred = H.bucket_embed_add(pred, bins, W, x, control, ctl_idx=src_idx if per_token else None,
+                                                scaled=True)
+        elif inference:
+            out, idx = H.bucket_embed_add(pred, bins, W, x, control)
             if control != 1.0:
                 pred = H.axpby(pred, None, control, 0.0)
         else:
-            out, idx = H.bucket_embed_add(target, S.b(pre + f"{name}_bins"), S.p(pre + f"{name}_embedding.weight"), x)
+            out, idx = H.bucket_embed_add(target, bins, W, x)
         return pred, out, (pctx, idx)
 
     def fwd(self, x, batch, src_lens, table, Tm, control, inference, teacher_forcing, text_emb=None):
@@ -138,6 +169,15 @@ class VarianceAdaptor:
         energy_p = pitch_p = None
         attn = dict(attn_logprob=None, attn_soft=None, attn_hard=None)
         dur_aligned = None
+        ctl = dict(energy=control.energy, pitch=control.pitch, duration=control.duration)
+        if inference:  # (training ignores the controls.)  Tensor controls: checked and moved before anything is launched
+            for name in ("energy", "pitch"):
+                if getattr(cfg, name).level.value == "phone":
+                    ctl[name] = self._control(name, ctl[name], B, Ts)
+                else:  # (free inference: the frame count comes with the durations; ``_variance`` checks against it)
+                    ctl[name] = self._control(name, ctl[name], B, Tm if teacher_forcing else None, Ts)
+            if not teacher_forcing:
+                ctl["duration"] = self._control("duration", ctl["duration"], B, Ts)
         if self.aligner is not None and (teacher_forcing or not inference):
             # fs2/variance_adaptor.py:249-305: soft alignment, MAS, durations, phone-level targets
             mel, mel_lens = batch["mel"], batch["mel_lens"]
@@ -164,9 +204,9 @@ class VarianceAdaptor:
         jobs = [] if (not inference and self._grouping()) else None
         res, c["pred_groups"] = {}, []
         if cfg.energy.level.value == "phone":
-            energy_p, x, c["energy"] = self._variance("energy", x, energy_t, src_lens, control.energy, inference, jobs)
+            energy_p, x, c["energy"] = self._variance("energy", x, energy_t, src_lens, ctl["energy"], inference, jobs)
         if cfg.pitch.level.value == "phone":
-            pitch_p, x, c["pitch"] = self._variance("pitch", x, pitch_t, src_lens, control.pitch, inference, jobs)
+            pitch_p, x, c["pitch"] = self._variance("pitch", x, pitch_t, src_lens, ctl["pitch"], inference, jobs)
         if jobs is not None:
             jobs.append(("duration", x, src_lens))
             c["pred_groups"] += self._run_predictors(jobs, res)
@@ -183,18 +223,28 @@ class VarianceAdaptor:
             dur = batch["duration"]
         else:
             # fs2/variance_adaptor.py:360-366: clamp(round(exp(logd) - 1) * control, min=0).int()
-            dur = H.duration_round(logd, control.duration)
+            dur = H.duration_round(logd, ctl["duration"])
             _, totals = H.duration_cumsum(dur, 1 << 30)
             Tm = int(min(int(totals.max()), int(Tm)))  # host sync (output size): inference only
             Tm = max(Tm, 1)
         frame_level = cfg.energy.level.value == "frame" or cfg.pitch.level.value == "frame"
-        x, cum, tgt_lens = H.length_regulate_fwd(x, dur, Tm, None if frame_level else table(Tm))
+        # a per-token [B, Ts] control of a frame-level predictor reaches its frames through the regulator's source index
+        # ([B, T] with Ts == Tm means frames)
+        src_idx = None
+        if inference and Ts != Tm and any(
+                getattr(cfg, n).level.value == "frame" and isinstance(ctl[n], torch.Tensor) and ctl[n].dim() == 2
+                and ctl[n].shape[1] == Ts and Ts != 1 for n in ("energy", "pitch")):
+            x, cum, tgt_lens, src_idx = H.length_regulate_fwd(x, dur, Tm, None, want_src_idx=True)
+        else:
+            x, cum, tgt_lens = H.length_regulate_fwd(x, dur, Tm, None if frame_level else table(Tm))
         c["cum"] = cum
         jobs = [] if jobs is not None else None
         if cfg.energy.level.value == "frame":
-            energy_p, x, c["energy"] = self._variance("energy", x, energy_t, tgt_lens, control.energy, inference, jobs)
+            energy_p, x, c["energy"] = self._variance("energy", x, energy_t, tgt_lens, ctl["energy"], inference, jobs,
+                                                      src_idx, Ts)
         if cfg.pitch.level.value == "frame":
-            pitch_p, x, c["pitch"] = self._variance("pitch", x, pitch_t, tgt_lens, control.pitch, inference, jobs)
+            pitch_p, x, c["pitch"] = self._variance("pitch", x, pitch_t, tgt_lens, ctl["pitch"], inference, jobs,
+                                                    src_idx, Ts)
         if jobs:
             c["pred_groups"] += self._run_predictors(jobs, res)
         for name in ("energy", "pitch"):  # grouped predictors: prediction and context arrive here
@@ -600,8 +650,11 @@ class FastSpeech2(_Base):
         elif H.GEMM_BF16 == 0 and self.training and not inference and FP32_TRANSPOSED:
             self.store.refresh_transposed_fp32()  # W^T of the K = 256 data-gradient weights (streaming fp32 kernel)
         control = control or InferenceControl()
-        if "duration_control" in batch and batch["duration_control"] and batch["duration_control"][0]:
-            control.duration = batch["duration_control"][0]
+        dc = batch.get("duration_control")
+        if dc is not None and len(dc):
+            # (fs2/model.py:154-157: the first item's value.)  A tensor is taken as it is: its value is not read here
+            if isinstance(dc[0], torch.Tensor) or dc[0]:
+                control.duration = dc[0]
         batch = self.prepare_batch(batch)
         teacher_forcing = bool(inference and batch.get("mel_lens") is not None)
         S, m = self.store, self.config.model

@@ -366,6 +366,14 @@ int fs2hip_onehot(const int* idx, float* out, int M, int Vp, int padding_idx, vo
 /* out = x + W[lower_bound(bins, val*control)]; idx_out (int32, bit-exact vs torch.bucketize) optional */
 int fs2hip_bucket_embed_add(const float* val, float control, const float* bins, int NB, const float* W,
                             const float* x, float* out, int* idx_out, int M, int D, void* stream);
+/* The same with the control in device memory (a tensor in InferenceControl): row r uses ctl[r / ctl_div] -- ctl_div = 1:
+ * one value per row, ctl_div = rows per utterance: one per utterance -- or, with ctl_idx (int [M], the length
+ * regulator's src_idx), ctl[(r / ctl_div) * ctl_T + ctl_idx[r]] with ctl_div = rows (frames) per utterance and ctl
+ * [M / ctl_div][ctl_T]; the control is exactly 1 where ctl_idx[r] is not in [0, ctl_T).  scaled (optional, [M]) receives
+ * val * control.  -22: ctl NULL, ctl_div <= 0, M % ctl_div != 0, D % 4 != 0, ctl_idx without ctl_T > 0. */
+int fs2hip_bucket_embed_add_ctl(const float* val, const float* ctl, int ctl_div, const int* ctl_idx, int ctl_T,
+                                const float* bins, int NB, const float* W, const float* x, float* out, int* idx_out,
+                                float* scaled, int M, int D, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * LengthRegulator (fs2/variance_adaptor.py:65-81): out[b, t] = x[b, j] for the token j whose
@@ -453,6 +461,9 @@ int fs2hip_scale_dev(float* x, long long n, const float* scalar, void* stream);
 int fs2hip_dact_mul(const float* dy, const float* aux, float* out, long long n, int act, void* stream);
 /* inference durations (fs2/variance_adaptor.py:360-366): out = int(max(rint(exp(logd) - 1) * control, 0)) */
 int fs2hip_duration_round(const float* logd, float control, int* out, int n, void* stream);
+/* the same with the control in device memory: element i uses ctl[i / ctl_div] (-22: ctl NULL, ctl_div <= 0,
+ * n % ctl_div != 0) */
+int fs2hip_duration_round_ctl(const float* logd, const float* ctl, int ctl_div, int* out, int n, void* stream);
 int fs2hip_mask_from_lens(const int* lens, unsigned char* mask, int B, int T, void* stream);
 int fs2hip_sum_slots(const float* x, int n, float* out, void* stream);
 
