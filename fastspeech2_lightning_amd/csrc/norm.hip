@@ -11,7 +11,8 @@ constexpr int LN_BWD_ROWS = 32;        // rows per workgroup in the backward (4 
 // a wavefront walks its rows one after the other (load, two wave reductions, store: a dependent chain of ~1.5 us per row),
 // so with 32 rows per workgroup the 4 096 rows of the encoder / the variance predictors are 128 workgroups on 256 CUs,
 // each wavefront 8 rows deep: 13 us for a kernel whose bytes take 3.  Short matrices take fewer rows per workgroup
-// (more workgroups, shallower chains); the price is more partial rows for the batched second stage, bounded at 512.
+// (more workgroups, shallower chains); the price is more partial rows for the batched second stage: at most 512 with 8
+// rows per workgroup (M <= 4 096), at most 1 024 with 16 (M <= 16 384), M / 32 above that (648 for the model's 20 736 rows).
 // FS2_LN_BWD_ROWS=8|16|32 (measurement aid): one value for every row count
 static inline int ln_bwd_rows(int M) {
   static const int forced = getenv("FS2_LN_BWD_ROWS") ? atoi(getenv("FS2_LN_BWD_ROWS")) : 0;
@@ -299,7 +300,7 @@ extern "C" int fs2hip_layernorm_bwd_blocks(int M) {
 extern "C" int fs2hip_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean,
                                     const float* rstd, const float* dx_add, float* dx, float* partial,
                                     float* dgamma, float* dbeta, int M, int C, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256) return FS2HIP_EINVAL;
+  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256 || !partial) return FS2HIP_EINVAL;
   if (((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)gamma % 16)) return FS2HIP_EINVAL;
   if (dx_add && ((uintptr_t)dx_add % 16)) return FS2HIP_EINVAL;
   const int nblk = fs2hip_layernorm_bwd_blocks(M);

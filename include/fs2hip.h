@@ -6,9 +6,12 @@
  * reference call site(s) (file:line, relative to the reference checkout) whose
  * ATen ops it replaces.  INTEGRATION.md shows the ctypes binding.
  *
- * Dropout: element i keeps iff its 16-bit field of hash(seed + *drop_step * c, i >> 1) >= p * 2^16, regenerated
- * (never stored) by the backward kernels; `drop_step` is a device-resident counter so that a
- * captured hipGraph draws a fresh mask on every replay.
+ * Dropout: element i keeps iff its 16-bit field (even i: low half, odd i: high half) of
+ * hash32(mix64(seed + *drop_step * 0xD1B54A32D192ED03), i >> 1) >= (uint32)(p * 65536 + 0.5), and is then scaled by
+ * 1/(1-p) in fp32; mix64 is the splitmix64 finaliser (applied with or without a counter), hash32 the two-round 32-bit
+ * mixer fs2_hash32 (csrc/common.h).  tests/layernorm_references.py restates the rule on the host and
+ * tests/test_layernorm_gpu.py holds the kernels to it.  The mask is regenerated (never stored) by the backward
+ * kernels; `drop_step` is a device-resident counter so that a captured hipGraph draws a fresh mask on every replay.
  *
  * Conventions (all entry points):
  *   - raw device pointers into caller-owned dense row-major buffers; activations
