@@ -3,6 +3,7 @@
 Lightning ``Trainer(gradient_clip_val=1.0, monitor="validation/total_loss", max_epochs, max_steps, ...)``).
 
     fs2l train CONFIG.yaml [-c training.batch_size=8 ...] [--devices N] [--resume last.ckpt]
+    fs2l synthesize CKPT [-t TEXT]... [-f FILELIST] [-o OUTPUT_DIR] ...   (``synthesize_command``, synthesis.py)
 
 What it does, in the reference's order: load the YAML/JSON config (+ ``-c key=value`` overrides), read
 ``<preprocessing.save_dir>/stats.json``, build the speaker / language look-up tables from the two filelists, build the
@@ -135,7 +136,41 @@ def build_parser() -> argparse.ArgumentParser:
     bm.add_argument("--warmup-reps", type=int, default=10)
     bm.add_argument("--repetitions", type=int, default=300)
     bm.add_argument("--precision", default="32-true", choices=["32-true", "32-split", "bf16-mixed"])
+    sy = sub.add_parser("synthesize", help="Given some text and a trained model, write predicted spectrograms (reference fs2/cli/synthesize.py)")
+    sy.add_argument("model_path", type=Path, help="a trained text-to-spec checkpoint")
+    sy.add_argument("-t", "--text", dest="texts", action="append", default=[], help="some text to synthesize; can be repeated")
+    sy.add_argument("-f", "--filelist", type=Path, default=None,
+                    help="'|'-separated filelist with a header (basename|characters|language|speaker), or plain text with one utterance per line")
+    sy.add_argument("-o", "--output-dir", type=Path, default=Path("synthesis_output"))
+    sy.add_argument("-l", "--language", default=None, help="language of a multilingual model (default: the first of its table)")
+    sy.add_argument("-s", "--speaker", default=None, help="speaker of a multispeaker model (default: the first of its table)")
+    sy.add_argument("-D", "--duration-control", type=float, default=1.0, help="multiplies the durations: lower is quicker")
+    sy.add_argument("--pitch-control", type=float, default=1.0, help="multiplies the predicted pitch (InferenceControl.pitch)")
+    sy.add_argument("--energy-control", type=float, default=1.0, help="multiplies the predicted energy (InferenceControl.energy)")
+    sy.add_argument("-S", "--style-reference", type=Path, default=None,
+                    help="a .pt file holding a [n_mels, frames] mel in the preprocessor's layout (GST models only)")
+    sy.add_argument("-T", "--teacher-forcing-directory", type=Path, default=None,
+                    help="ADVANCED. preprocessed folder with spec and duration / attn folders to teacher-force the outputs")
+    sy.add_argument("-b", "--batch-size", type=int, default=4)
+    sy.add_argument("-O", "--output-type", action="append", type=_output_type, default=None,
+                    help="'spec': [n_mels, frames] .pt tensors (the only format written here)")
+    sy.add_argument("--text-representation", choices=["characters", "phones"], default="characters")
+    sy.add_argument("--precision", default="32-true", choices=["32-true", "32-split", "bf16-mixed"])
+    sy.add_argument("--no-sort", action="store_true", help="batches in input order instead of sorted by length (longest first)")
+    sy.add_argument("--dry-run", action="store_true", help="resolve entries, batches and file names, print them as JSON, touch no GPU")
     return ap
+
+
+def _output_type(value: str) -> str:
+    needs = {"wav": "a vocoder (spec-to-wav model)", "textgrid": "the parent toolkit's TextGrid writer",
+             "readalong-xml": "the parent toolkit's ReadAlong writer",
+             "readalong-html": "a vocoder and the parent toolkit's ReadAlong writer"}
+    if value == "spec":
+        return value
+    if value in needs:
+        raise argparse.ArgumentTypeError(f"output type {value!r} needs {needs[value]}, which is not part of this project: "
+                                         "only 'spec' is written (feed the .pt files to your vocoder)")
+    raise argparse.ArgumentTypeError(f"unknown output type {value!r}: only 'spec' is written")
 
 
 def plan(args) -> dict:
@@ -606,6 +641,92 @@ def benchmark(args) -> int:
     return 0
 
 
+def checkpoint_tables(ckpt: dict):
+    """What the data side of ``synthesize`` needs of a model, from a checkpoint's ``hyper_parameters`` alone (no GPU, no
+    weights): ``config``, ``lang2id``, ``speaker2id``."""
+    from types import SimpleNamespace
+
+    from .config import FastSpeech2Config
+    hp = ckpt["hyper_parameters"]
+    config = hp["config"]
+    if not isinstance(config, FastSpeech2Config):
+        config = FastSpeech2Config(**config)
+    return SimpleNamespace(config=config, lang2id=dict(hp.get("lang2id") or {}), speaker2id=dict(hp.get("speaker2id") or {}))
+
+
+def synthesis_file_names(dataset, out_dir, global_step: int) -> list:
+    """The files ``PackedSpecWriter`` will write for ``dataset``, in input order (one per text: chunks are joined)."""
+    from .data import SEP, slugify, truncate_basename
+    audio = dataset.config.preprocessing.audio
+    suffix = f"spec-pred-{audio.input_sampling_rate}-{getattr(audio, 'spec_type', 'mel-librosa')}.pt"
+    names, text = [], ""
+    for e in dataset.entries:
+        text += e.get("characters", e.get("phones", "text"))  # (``raw_text`` of the item)
+        if e.get("is_last_input_chunk", True):
+            names.append(str(Path(out_dir) / "synthesized_spec" / SEP.join(
+                [truncate_basename(slugify(text)), e.get("speaker") or "default", e.get("language") or "default",
+                 f"ckpt={global_step}", suffix])))
+            text = ""
+    return names
+
+
+def synthesize_command(args) -> int:
+    """``fs2l synthesize`` (reference ``fs2/cli/synthesize.py:466-700``): checkpoint + text -> ``.pt`` spectrograms in
+    ``OUTPUT_DIR/synthesized_spec/``, one GPU.  Argument errors come before anything expensive is loaded."""
+    from .config import TargetTrainingTextRepresentationLevel as L
+    if not args.texts and not args.filelist:
+        print("You must define either --text or --filelist", file=sys.stderr)
+        raise SystemExit(1)
+    if args.style_reference is not None and args.style_reference.suffix != ".pt":
+        raise SystemExit(f"--style-reference {args.style_reference}: expected a .pt file holding a [n_mels, frames] mel; turning "
+                         "audio into a mel needs the parent toolkit's preprocessor")
+    if args.batch_size < 1:
+        raise SystemExit("--batch-size must be at least 1")
+    from .data import PackedSpecWriter, SynthesisDataset, synthesis_batches, synthesis_entries
+    print(f"Loading checkpoint from {args.model_path}", file=sys.stderr)
+    if args.dry_run:
+        ckpt = torch.load(args.model_path, map_location="cpu", weights_only=False)
+        model = checkpoint_tables(ckpt)
+    else:
+        from .model import FastSpeech2
+        model, ckpt = FastSpeech2.load_from_checkpoint(args.model_path, precision=args.precision, return_checkpoint=True)
+    global_step = int(ckpt.get("global_step", 0))
+    config = model.config
+    if config.model.target_text_representation_level == L.characters and args.text_representation != "characters":
+        raise ValueError(f"Your model was trained on {config.model.target_text_representation_level} but you provided "
+                         f"{args.text_representation} which is incompatible.")
+    style = None
+    if args.style_reference is not None:
+        style = torch.load(args.style_reference, map_location="cpu", weights_only=True)
+    entries = synthesis_entries(args.texts, args.filelist, args.language, args.speaker, args.duration_control, model,
+                                args.text_representation)
+    dataset = SynthesisDataset(entries, config, model.lang2id, model.speaker2id,
+                               teacher_forcing_dir=args.teacher_forcing_directory, style_reference=style)
+    sort = not args.no_sort
+    if args.dry_run:
+        print(json.dumps({
+            "checkpoint": str(args.model_path), "global_step": global_step, "output_dir": str(args.output_dir),
+            "utterances": len(dataset), "batch_size": args.batch_size, "sort": sort,
+            "token_counts": dataset.token_counts, "dropped_symbols": dataset.dropped,
+            "batches": synthesis_batches(dataset.token_counts, args.batch_size, sort),
+            "entries": [{k: e.get(k) for k in ("basename", "language", "speaker", "duration_control")} for e in entries],
+            "files": synthesis_file_names(dataset, args.output_dir, global_step)}))
+        return 0
+    from .config import InferenceControl
+    from .synthesis import synthesize
+    audio = config.preprocessing.audio
+    writer = PackedSpecWriter(args.output_dir, model.output_key, global_step, audio.input_sampling_rate,
+                              getattr(audio, "spec_type", "mel-librosa"), n_mels=audio.n_mels)
+    control = InferenceControl(pitch=args.pitch_control, energy=args.energy_control, duration=args.duration_control)
+    t0 = time.perf_counter()
+    res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort)
+    torch.cuda.synchronize()
+    print(json.dumps({"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
+                      "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),
+                      "output_dir": str(writer.dir)}), flush=True)
+    return 0
+
+
 def main(argv: Optional[list] = None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     args = build_parser().parse_args(argv)
@@ -613,6 +734,8 @@ def main(argv: Optional[list] = None) -> int:
         return train(args, argv)
     if args.command == "benchmark":
         return benchmark(args)
+    if args.command == "synthesize":
+        return synthesize_command(args)
     return 2
 
 

@@ -1,5 +1,7 @@
 """Batch producer for the hot path: per-utterance feature files -> collated
-batch dict -> pinned, asynchronously prefetched device batches; spectrogram writer; validation loop.
+batch dict -> pinned, asynchronously prefetched device batches; spectrogram writers; validation loop; and the data
+side of ``fs2l synthesize``: text -> inference items -> length-sorted batches (``synthesis_entries``, ``SynthesisDataset``,
+``synthesis_batches``, ``PackedSpecWriter``).
 
 Restates, without the parent toolkit, the parts of the reference that sit directly either side of the step:
   * on-disk layout ``<save_dir>/<kind>/<basename>--<speaker>--<language>--<suffix>.pt`` and the item dict of
@@ -27,8 +29,7 @@ def feature_path(save_dir, kind: str, basename: str, speaker: str, language: str
 
 
 class FeatureDataset(torch.utils.data.Dataset):
-    """Training / teacher-forcing items of ``FastSpeechDataset`` (the text-processing inference branch belongs to
-    the parent toolkit and is out of scope)."""
+    """Training / teacher-forcing items of ``FastSpeechDataset`` (the inference branch: ``SynthesisDataset``)."""
 
     def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, text_processor=None):
         from .config import TextProcessor
@@ -401,6 +402,262 @@ class SpecWriter:
                 written.append(path)
                 self._spec, self._text = torch.tensor(()), ""
         return written
+
+
+class PackedSpecWriter(SpecWriter):
+    """``SpecWriter`` for batches that left the GPU packed (``hip.pack_spec``): same directory, file names and suffix, one
+    contiguous ``[n_mels, frames]`` fp32 tensor per file.  ``write_packed`` takes a batch's packed HOST tensor, its
+    offsets, the batch (for ``raw_text`` / ``speaker`` / ``language`` / ``is_last_input_chunk``) and the items' positions
+    in the input.  Files are written in INPUT order whatever order the batches come in: a piece is held (as a copy of its
+    own: the caller reuses the packed buffer) until every earlier position has arrived, and consecutive chunks of one
+    text are concatenated along frames until ``is_last_input_chunk`` -- also when sorting by length has put the chunks
+    into different batches."""
+
+    def __init__(self, out_dir, output_key: str, global_step: int = 0, sampling_rate: int = 22050,
+                 spec_type: str = "mel-librosa", n_mels: int = 80):
+        super().__init__(out_dir, output_key, global_step, sampling_rate, spec_type)
+        self.n_mels = int(n_mels)
+        self._held, self._next, self._chunks = {}, 0, []
+
+    def write_packed(self, packed: torch.Tensor, offsets, batch: dict, positions) -> list[Path]:
+        offsets = [int(o) for o in offsets]
+        last = batch.get("is_last_input_chunk") or [True] * len(positions)
+        if len(offsets) != len(positions) + 1:
+            raise ValueError(f"PackedSpecWriter: {len(offsets)} offsets for {len(positions)} utterances")
+        for i, pos in enumerate(positions):
+            lo, hi = offsets[i], offsets[i + 1]
+            if hi < lo or (hi - lo) % self.n_mels or hi > packed.numel():
+                raise ValueError(f"PackedSpecWriter: offsets {lo}..{hi} do not delimit a [{self.n_mels}, frames] block")
+            if int(pos) in self._held or int(pos) < self._next:
+                raise ValueError(f"PackedSpecWriter: position {int(pos)} delivered twice")
+            spec = packed[lo:hi].reshape(self.n_mels, (hi - lo) // self.n_mels).clone()
+            self._held[int(pos)] = (spec, batch["raw_text"][i], batch["speaker"][i], batch["language"][i],
+                                    last[i] is None or bool(last[i]))
+        written = []
+        while self._next in self._held:
+            spec, text, speaker, language, is_last = self._held.pop(self._next)
+            self._next += 1
+            self._chunks.append(spec)
+            self._text += text
+            if is_last:
+                path = self.filename(truncate_basename(slugify(self._text)), speaker, language)
+                torch.save(torch.cat(self._chunks, -1) if len(self._chunks) > 1 else self._chunks[0], path)
+                written.append(path)
+                self._chunks, self._text = [], ""
+        return written
+
+    def pending(self) -> int:
+        """Pieces held back: positions not yet reached, plus chunks of a text whose last chunk has not arrived."""
+        return len(self._held) + len(self._chunks)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# synthesis: text -> inference items -> batches (reference fs2/cli/synthesize.py:136-319, fs2/dataset.py:88-224)
+# ----------------------------------------------------------------------------------------------------------------------
+def _check_keys(data_keys: set, model_keys: set, key: str, multi: bool):
+    """In the spirit of the reference's ``validate_data_keys_with_model_keys`` (fs2/cli/synthesize.py:27-72): a speaker /
+    language the model has no embedding row for ends the command with a message that names it."""
+    extras = sorted(str(k) for k in data_keys - model_keys - {None})
+    if not extras:
+        return
+    if multi:
+        raise SystemExit(f"You provided {extras} which {'is not a' if len(extras) == 1 else 'are not'} {key}"
+                         f"{'' if len(extras) == 1 else 's'} supported by the model {sorted(model_keys)}.")
+    raise SystemExit(f"The current model doesn't support multiple {key}s but your data has {key}s {extras}.\n"
+                     f"Please retrain your model with multi{'lingual' if key == 'language' else key} set to True.")
+
+
+def _filelist_rows(path, text_key: str):
+    """Rows of a '|'-separated filelist whose header names the text column, else None (a plain-text file)."""
+    import csv
+    with open(path, encoding="utf8", newline="") as f:
+        header = f.readline().rstrip("\r\n").split("|")
+    if text_key not in header:
+        return None
+    if "basename" in header:
+        from .cli import read_filelist
+        return read_filelist(path)
+    with open(path, encoding="utf8", newline="") as f:
+        return list(csv.DictReader(f, delimiter="|", quoting=csv.QUOTE_NONE))
+
+
+def synthesis_entries(texts, filelist, language, speaker, duration_control, model,
+                      text_representation: str = "characters") -> list[dict]:
+    """The reference's ``prepare_data`` / ``load_data_from_filelist`` (fs2/cli/synthesize.py:136-319) without text
+    chunking (the parent toolkit's ``chunk_text``): every text is one entry with ``is_last_input_chunk = True``.
+
+    ``texts`` wins over ``filelist`` (with the reference's note on stderr).  A filelist is the preprocessor's
+    '|'-separated format with a header (``basename|characters|language|speaker``; token columns are kept when present)
+    or, when its first line does not name the text column, plain text with one utterance per line (blanks around a line
+    and empty lines dropped).  A row without a basename gets ``truncate_basename(slugify(text))``.  ``language`` /
+    ``speaker`` override the rows'; the defaults are the first keys of the model's look-up tables.  ``model`` only needs
+    ``lang2id``, ``speaker2id`` and ``config.model.multilingual`` / ``multispeaker``."""
+    import sys
+    key = text_representation
+    default_language = next(iter(model.lang2id), None)
+    default_speaker = next(iter(model.speaker2id), None)
+    data = []
+    if texts:
+        if filelist:
+            print("Got arguments for both text and a filelist - this will only process the text."
+                  " Please re-run without providing text if you want to run batch synthesis on the provided file.",
+                  file=sys.stderr)
+        for text in texts:
+            data.append({"basename": truncate_basename(slugify(text)), key: text,
+                         "language": language or default_language, "speaker": speaker or default_speaker})
+    else:
+        if filelist is None:
+            raise ValueError("Filelist must be provided when texts is empty or None")
+        rows = _filelist_rows(filelist, key)
+        if rows is not None:
+            for r in rows:
+                text = r.get(key) or ""
+                e = {"basename": r.get("basename") or truncate_basename(slugify(text)), key: text,
+                     "language": language or r.get("language") or default_language,
+                     "speaker": speaker or r.get("speaker") or default_speaker}
+                for col in ("character_tokens", "phone_tokens"):
+                    if r.get(col):
+                        e[col] = r[col]
+                data.append(e)
+        else:
+            with open(filelist, encoding="utf8") as f:
+                for line in f:
+                    text = line.strip()
+                    if text:
+                        data.append({"basename": truncate_basename(slugify(text)), key: text,
+                                     "language": language or default_language, "speaker": speaker or default_speaker})
+    if not data:
+        raise SystemExit("Nothing to synthesize: no text was given")
+    m = model.config.model
+    _check_keys({d["language"] for d in data}, set(model.lang2id), "language", m.multilingual)
+    _check_keys({d["speaker"] for d in data}, set(model.speaker2id), "speaker", m.multispeaker)
+    for d in data:
+        d["is_last_input_chunk"] = True
+        d["duration_control"] = duration_control if duration_control else 1.0
+    return data
+
+
+def synthesis_batches(token_counts, batch_size: int, sort: bool = True) -> list[list[int]]:
+    """Batch composition of ``synthesize``: item indices sorted by token count, longest first (a stable sort: equal counts
+    keep their input order), cut into consecutive groups of ``batch_size``; ``sort=False``: input order."""
+    if batch_size < 1:
+        raise ValueError("synthesis_batches: batch_size >= 1")
+    order = list(range(len(token_counts)))
+    if sort:
+        order.sort(key=lambda i: -int(token_counts[i]))
+    return [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+
+
+class SynthesisDataset(torch.utils.data.Dataset):
+    """The inference branch of the reference's ``FastSpeechDataset.__getitem__`` (fs2/dataset.py:88-98, :109-110,
+    :153-154, :192-194, :212-214): the 15 keys of ``FeatureDataset``'s items in the same order, with ``mel`` /
+    ``duration`` / ``energy`` / ``pitch`` None in free synthesis, ``is_last_input_chunk`` (default True) and
+    ``duration_control`` from the entry.  With ``teacher_forcing_dir`` the mel and the durations (the attention prior of
+    a model that learns its alignment) are loaded from that directory exactly as ``FeatureDataset`` loads them.
+
+    Tokens: the entry's ``character_tokens`` / ``phone_tokens`` column through ``encode_escaped_string_sequence`` when
+    present, else its raw ``characters`` / ``phones`` text through ``TextProcessor.encode_text``.  There is no G2P, no
+    text cleaning and no chunking here: those belong to the parent toolkit, which is not part of the reference
+    repository -- so a phone model needs phones, and a ``phonological_features`` model, whose feature vectors only the
+    parent toolkit computes, is refused in free synthesis (with a teacher-forcing directory ``pfs.pt`` is loaded as in
+    training).  Symbols the table does not hold are dropped as ``TextProcessor`` drops them; how many is reported once
+    on stderr, and an utterance left without a token is an error that names it.
+
+    ``style_reference``: a ``[n_mels, frames]`` mel (the preprocessor's spectrogram layout), attached to every item as
+    ``mel_style_reference`` ``[frames, n_mels]``; refused by a model without the GST module.  Every text is encoded in the
+    constructor: ``token_counts`` is what ``synthesis_batches`` takes."""
+
+    def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, teacher_forcing_dir=None,
+                 style_reference=None, text_processor=None):
+        import sys
+
+        from .config import TargetTrainingTextRepresentationLevel as L
+        from .config import TextProcessor
+
+        self.entries, self.config = entries, config
+        self.lang2id, self.speaker2id = lang2id, speaker2id
+        self.text_processor = text_processor or TextProcessor(config.text)
+        m, audio = config.model, config.preprocessing.audio
+        self.teacher_forcing = teacher_forcing_dir is not None
+        self.save_dir = Path(teacher_forcing_dir) if self.teacher_forcing else None
+        self.sampling_rate = audio.input_sampling_rate
+        self.spec_type = getattr(audio, "spec_type", "mel-librosa")
+        self.chars = m.target_text_representation_level == L.characters
+        self.use_pfs = m.target_text_representation_level == L.phonological_features
+        if self.use_pfs and not self.teacher_forcing:
+            raise ValueError("a phonological_features model needs feature vectors that only the parent toolkit computes: "
+                             "free synthesis is not possible here (teacher forcing loads the stored pfs.pt)")
+        self.style = None
+        if style_reference is not None:
+            if not m.use_global_style_token_module:
+                raise ValueError("a style reference needs a model trained with the global style token module "
+                                 "(model.use_global_style_token_module)")
+            ref = torch.as_tensor(style_reference, dtype=torch.float32)
+            ref = ref.squeeze(0) if ref.dim() == 3 else ref
+            if ref.dim() != 2 or ref.shape[0] != audio.n_mels or ref.shape[1] < 1:
+                raise ValueError(f"style reference must be a [n_mels = {audio.n_mels}, frames] mel, got {list(ref.shape)}")
+            self.style = ref.transpose(0, 1).contiguous()
+        tok_key, raw_key = ("character_tokens", "characters") if self.chars else ("phone_tokens", "phones")
+        self.tokens, dropped = [], 0
+        for e in entries:
+            if e.get(tok_key):
+                ids = self.text_processor.encode_escaped_string_sequence(e[tok_key])
+                seq = e[tok_key]
+                n_in = len(seq) if not isinstance(seq, str) else 1 + sum(
+                    1 for i, ch in enumerate(seq) if ch == "/" and (i == 0 or seq[i - 1] != "\\"))
+                dropped += n_in - len(ids)
+            elif e.get(raw_key) is not None:
+                ids = self.text_processor.encode_text(e[raw_key])
+                dropped += len(e[raw_key]) - sum(len(self.text_processor.symbols[i]) for i in ids)
+            else:
+                raise ValueError(f"utterance {e.get('basename')!r} has neither {tok_key!r} nor {raw_key!r}: the model reads "
+                                 f"{raw_key} (turning characters into phones is the parent toolkit's G2P)")
+            if not ids:
+                raise ValueError(f"utterance {e.get('basename')!r} ({e.get(raw_key, e.get(tok_key))!r}) has no symbol of the "
+                                 "model's symbol table: nothing to synthesize")
+            self.tokens.append(torch.IntTensor(ids))
+        self.dropped = dropped
+        if dropped:
+            print(f"{dropped} input symbol(s) are not in the model's symbol table and were dropped", file=sys.stderr)
+
+    _load = FeatureDataset._load
+
+    def __len__(self):
+        return len(self.entries)
+
+    @property
+    def token_counts(self) -> list:
+        return [len(t) for t in self.tokens]
+
+    def __getitem__(self, index):
+        item = self.entries[index]
+        speaker, language = item.get("speaker") or "default", item.get("language") or "default"
+        bn = item["basename"]
+        m = self.config.model
+        mel = duration = pfs = None
+        if self.teacher_forcing:
+            mel = self._load(bn, speaker, language, "spec", f"spec-{self.sampling_rate}-{self.spec_type}.pt").transpose(0, 1)
+            if m.learn_alignment:
+                duration = self._load(bn, speaker, language, "attn",
+                                      ("characters" if self.chars else "phones") + "-attn-prior.pt")
+            else:
+                try:
+                    duration = self._load(bn, speaker, language, "duration", "duration.pt")
+                except FileNotFoundError as e:
+                    raise ValueError("model.learn_alignment = false requires text/audio alignments in "
+                                     "'<teacher forcing directory>/duration' (fs2/dataset.py:144-151)") from e
+            if self.use_pfs:
+                pfs = self._load(bn, speaker, language, "pfs", "pfs.pt")
+        last = item.get("is_last_input_chunk")
+        return {
+            "mel": mel, "mel_style_reference": self.style, "duration": duration,
+            "duration_control": item.get("duration_control", 1.0), "pfs": pfs, "text": self.tokens[index],
+            "raw_text": item.get("characters", item.get("phones", "text")), "basename": bn,
+            "speaker": speaker, "speaker_id": self.speaker2id.get(speaker, 0) if not m.multispeaker else self.speaker2id[speaker],
+            "language": language, "language_id": self.lang2id.get(language, 0) if not m.multilingual else self.lang2id[language],
+            "energy": None, "pitch": None,
+            "is_last_input_chunk": True if last is None else bool(last),
+        }
 
 
 def slugify(text: str) -> str:

@@ -148,6 +148,7 @@ SIGNATURES = {
     "fs2hip_act_apply": "ppqip",
     "fs2hip_memset": "piqp",
     "fs2hip_pad_batch": None,  # (const Fs2PadMember*, int, void*): set below
+    "fs2hip_pack_spec": "ppppiiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -1921,6 +1922,29 @@ def pad_batch(batch: dict, Ts_b: int, Tm_b: int, out: Optional[dict] = None, fra
     res.pop("bucket_geometry", None)
     res.pop("bucket_leftover", None)
     return res
+
+
+def pack_spec(y, lens, packed=None, offsets=None):
+    """``y`` [B, Tm, C] fp32 (a model output), ``lens`` [B] int32 (``tgt_lens``) -> ``(packed, offsets)``: every
+    utterance's ``y[b, :len_b].T`` -- [C, len_b], the layout of the spectrogram files -- back to back in ``packed``
+    (``B * Tm * C`` floats, the worst case; only ``packed[:offsets[B]]`` is written) and ``offsets`` [B + 1] int64, element
+    offsets of the utterances with the total last, computed on the device from ``lens``.  Nothing is read back."""
+    _chk(y, torch.float32, "y")
+    _chk(lens, torch.int32, "lens")
+    _req(y.dim() == 3, f"pack_spec: y must be [B, Tm, C], got {tuple(y.shape)}")
+    B, Tm, C_ = y.shape
+    _req(B > 0 and Tm > 0 and C_ > 0, f"pack_spec: empty y {tuple(y.shape)}")
+    _req(lens.numel() == B, f"pack_spec: lens has {lens.numel()} entries for {B} utterances")
+    if packed is None:
+        packed = torch.empty(B * Tm * C_, device=y.device, dtype=torch.float32)
+    if offsets is None:
+        offsets = torch.empty(B + 1, device=y.device, dtype=torch.int64)
+    _chk(packed, torch.float32, "packed")
+    _chk(offsets, torch.int64, "offsets")
+    _req(packed.numel() >= B * Tm * C_, f"pack_spec: packed holds {packed.numel()} floats, the worst case is {B * Tm * C_}")
+    _req(offsets.numel() >= B + 1, f"pack_spec: offsets holds {offsets.numel()} entries, {B + 1} are written")
+    _ok(lib().fs2hip_pack_spec(_p(y), _p(lens), _p(packed), _p(offsets), B, Tm, C_, _stream()), "pack_spec")
+    return packed, offsets
 
 
 # ------------------------------------------------------------------------------------------

@@ -74,6 +74,7 @@ class VarianceAdaptor:
         self.S, self.env, self.config = S, env, config
         self.bad_count = None  # set by the model: persistent device word counting duration / mel_lens mismatches
         self.bad_probe = None  # set by the model: called right behind the kernel that bumps bad_count (training steps)
+        self.host_totals = None  # the last forward's per-utterance frame totals [B] on the host (free inference only)
         vp, d = config.model.variance_predictors, config.model.encoder.input_dim
         pre = "variance_adaptor."
         # declaration order = execution order: energy, pitch, duration
@@ -164,6 +165,8 @@ class VarianceAdaptor:
         cfg = self.config.model.variance_predictors
         B, Ts, D = x.shape
         c = {}
+        if inference:
+            self.host_totals = None
         energy_t = None if inference else batch["energy"]
         pitch_t = None if inference else batch["pitch"]
         energy_p = pitch_p = None
@@ -225,7 +228,10 @@ class VarianceAdaptor:
             # fs2/variance_adaptor.py:360-366: clamp(round(exp(logd) - 1) * control, min=0).int()
             dur = H.duration_round(logd, ctl["duration"])
             _, totals = H.duration_cumsum(dur, 1 << 30)
-            Tm = int(min(int(totals.max()), int(Tm)))  # host sync (output size): inference only
+            # host sync (output size): inference only.  The one read brings every utterance's frame total, not just the
+            # maximum: ``synthesize`` sizes the batch's device-to-host copy from it without a second synchronisation
+            self.host_totals = totals.cpu()
+            Tm = int(min(int(self.host_totals.max()), int(Tm)))
             Tm = max(Tm, 1)
         frame_level = cfg.energy.level.value == "frame" or cfg.pitch.level.value == "frame"
         # a per-token [B, Ts] control of a frame-level predictor reaches its frames through the regulator's source index

@@ -1,0 +1,119 @@
+"""Bulk synthesis: ``synthesize`` runs free (or teacher-forced) inference batch by batch and hands every batch's
+spectrograms to a ``PackedSpecWriter`` -- what ``fs2l synthesize`` runs (reference ``fs2/cli/synthesize.py:333-462``,
+whose Trainer.predict + prediction-writing callback read every utterance back on its own).
+
+A batch leaves the GPU through one kernel and one copy: ``hip.pack_spec`` trims, transposes and packs the batch's
+``[B, Tm, n_mels]`` output into one device buffer (the offsets in front of the payload), and ONE ``non_blocking``
+device-to-host copy on a copy stream brings offsets and payload into pinned memory.  The copy's size is known without
+asking the GPU again: free inference already reads the frame totals once per batch for the output length
+(``VarianceAdaptor.host_totals``), a teacher-forced batch has ``mel_lens`` on the host.  The host waits for a batch's
+copy event only after the NEXT batch's forward has been enqueued (``depth`` device / pinned buffer pairs in rotation;
+``depth = 1`` is the fully synchronous form and writes identical files).
+
+A file is what ``forward(inference=True)`` gives for the utterance IN THE BATCH ``data.synthesis_batches`` puts it in
+(padding, and therefore the kernels' tile choice, follow the batch); ``sort=False`` with ``batch_size = 1`` reproduces
+the reference's one-by-one behaviour.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import hip as H
+from .data import collate, synthesis_batches
+
+
+class _Slot:
+    """One device buffer + its pinned host twin, both float32: [header | payload].  The header holds the batch's B + 1
+    int64 offsets (2 floats each, rounded up to 4 floats so that the payload starts 16-byte aligned)."""
+
+    def __init__(self, device):
+        self.device, self.dev, self.host = device, None, None
+
+    @staticmethod
+    def header(B: int) -> int:
+        return -(-2 * (B + 1) // 4) * 4
+
+    def reserve(self, floats: int):
+        if self.dev is None or self.dev.numel() < floats:
+            n = max(floats, 1 << 16)
+            self.dev = torch.empty(n, device=self.device, dtype=torch.float32)
+            self.host = torch.empty(n, dtype=torch.float32).pin_memory()
+
+
+def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2) -> dict:
+    """Synthesizes every item of ``dataset`` (``data.SynthesisDataset``) and writes the spectrograms through ``writer``
+    (``data.PackedSpecWriter``), in input order.  Returns ``{"files": [paths], "utterances": n, "frames": n, "batches": n}``.
+    Per batch the host reads the GPU once inside the forward pass (the frame totals; nothing for a teacher-forced batch)
+    and waits once, for the copy event."""
+    if depth < 1:
+        raise ValueError("synthesize: depth >= 1")
+    if writer is None:
+        raise ValueError("synthesize: a PackedSpecWriter is required")
+    device = model.device_
+    n_mels = model.config.preprocessing.audio.n_mels
+    learn_alignment = model.config.model.learn_alignment
+    batches = synthesis_batches(dataset.token_counts, batch_size, sort)
+    was_training = model.training
+    model.eval()
+    files, frames = [], 0
+    pending = []   # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions)], oldest first
+
+    def finish(job):
+        nonlocal frames
+        slot, event, hdr, total, expect, cpu_batch, positions = job
+        event.synchronize()   # the one wait of this batch
+        offsets = slot.host[:2 * len(expect)].view(torch.int64)
+        if offsets.tolist() != expect:
+            raise RuntimeError("synthesize: the frame counts on the GPU differ from the host's (durations that do not add "
+                               f"up to the mel lengths?): offsets {offsets.tolist()} against {expect}")
+        files.extend(writer.write_packed(slot.host[hdr:hdr + total], offsets, cpu_batch, positions))
+        frames += total // n_mels
+
+    try:
+        with torch.cuda.device(device):
+            main = torch.cuda.current_stream(device)
+            copy_stream = torch.cuda.Stream(device=device)
+            slots = [_Slot(device) for _ in range(depth)]
+            for i, positions in enumerate(batches):
+                cpu_batch = collate([dataset[j] for j in positions], learn_alignment=learn_alignment, pin_memory=True)
+                out = model(cpu_batch, _copy_control(control), inference=True)
+                y = out[model.output_key]
+                B, Tm, C = y.shape
+                if cpu_batch["mel_lens"] is not None:
+                    lens_host = cpu_batch["mel_lens"].clamp(0, Tm)
+                else:
+                    lens_host = model.variance_adaptor.host_totals.clamp(0, Tm)
+                expect = [0]
+                for n in lens_host.tolist():
+                    expect.append(expect[-1] + int(n) * C)
+                hdr, total = _Slot.header(B), expect[-1]
+                slot = slots[i % depth]   # (its previous batch, i - depth, has been finished: see the drain below)
+                slot.reserve(hdr + B * Tm * C)
+                H.pack_spec(y, out["tgt_lens"], slot.dev[hdr:hdr + B * Tm * C], slot.dev[:2 * (B + 1)].view(torch.int64))
+                packed_ev = torch.cuda.Event()
+                packed_ev.record(main)
+                copy_stream.wait_event(packed_ev)
+                with torch.cuda.stream(copy_stream):
+                    slot.host[:hdr + total].copy_(slot.dev[:hdr + total], non_blocking=True)
+                    copied_ev = torch.cuda.Event()
+                    copied_ev.record(copy_stream)
+                slot.dev.record_stream(copy_stream)
+                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions))
+                # the next batch's forward is enqueued before this batch's copy is waited for: only what exceeds
+                # depth - 1 batches in flight is finished now
+                while len(pending) > depth - 1:
+                    finish(pending.pop(0))
+            while pending:
+                finish(pending.pop(0))
+    finally:
+        model.train(was_training)
+    if writer.pending():
+        raise RuntimeError(f"synthesize: {writer.pending()} piece(s) were never written (a text without a last chunk?)")
+    return {"files": files, "utterances": len(dataset), "frames": frames, "batches": len(batches)}
+
+
+def _copy_control(control) -> Optional[object]:
+    """``forward`` writes the batch's ``duration_control`` into the control it is given: every batch gets its own."""
+    return None if control is None else control.model_copy()

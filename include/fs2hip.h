@@ -561,6 +561,16 @@ typedef struct {
 } Fs2PadMember;
 int fs2hip_pad_batch(const Fs2PadMember* members, int n, void* stream);
 
+/* The way out of the GPU for a batch of predicted spectrograms (fs2/prediction_writing_callback.py:257-262 stores
+ * [K bands, T frames] per utterance): y [B][Tm][C] fp32, lens [B] (clamped to 0..Tm here).  For every utterance b the
+ * [C][len_b] transpose of y[b, :len_b, :] is written contiguously at packed + offsets[b]; offsets [B + 1] is produced
+ * here from lens (a one-workgroup prologue launch): offsets[b] = C * (len_0 + ... + len_{b-1}), offsets[B] = the total.
+ * Rows at and beyond len_b are never read; a length of 0 contributes nothing.  packed holds B * Tm * C floats (the worst
+ * case): nothing outside packed[0 .. offsets[B]) and offsets[0 .. B] is written whatever lens holds.  Any C, Tm >= 1;
+ * no alignment is required beyond the element types'. */
+int fs2hip_pack_spec(const float* y, const int* lens, float* packed, long long* offsets, int B, int Tm, int C,
+                     void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
