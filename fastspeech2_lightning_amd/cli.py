@@ -157,6 +157,9 @@ def build_parser() -> argparse.ArgumentParser:
     sy.add_argument("--text-representation", choices=["characters", "phones"], default="characters")
     sy.add_argument("--precision", default="32-true", choices=["32-true", "32-split", "bf16-mixed"])
     sy.add_argument("--no-sort", action="store_true", help="batches in input order instead of sorted by length (longest first)")
+    sy.add_argument("--exact-lengths", action="store_true",
+                    help="every file is what the utterance gives when it is synthesized alone, whatever -b and the sort order are "
+                         "(the padded rows are zeroed on the GPU in front of every convolution over time; a few dozen small launches per batch)")
     sy.add_argument("--dry-run", action="store_true", help="resolve entries, batches and file names, print them as JSON, touch no GPU")
     return ap
 
@@ -707,6 +710,7 @@ def synthesize_command(args) -> int:
         print(json.dumps({
             "checkpoint": str(args.model_path), "global_step": global_step, "output_dir": str(args.output_dir),
             "utterances": len(dataset), "batch_size": args.batch_size, "sort": sort,
+            "exact_lengths": bool(args.exact_lengths),
             "token_counts": dataset.token_counts, "dropped_symbols": dataset.dropped,
             "batches": synthesis_batches(dataset.token_counts, args.batch_size, sort),
             "entries": [{k: e.get(k) for k in ("basename", "language", "speaker", "duration_control")} for e in entries],
@@ -719,7 +723,7 @@ def synthesize_command(args) -> int:
                               getattr(audio, "spec_type", "mel-librosa"), n_mels=audio.n_mels)
     control = InferenceControl(pitch=args.pitch_control, energy=args.energy_control, duration=args.duration_control)
     t0 = time.perf_counter()
-    res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort)
+    res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort, exact_lengths=args.exact_lengths)
     torch.cuda.synchronize()
     print(json.dumps({"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
                       "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),

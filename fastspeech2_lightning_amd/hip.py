@@ -149,6 +149,7 @@ SIGNATURES = {
     "fs2hip_memset": "piqp",
     "fs2hip_pad_batch": None,  # (const Fs2PadMember*, int, void*): set below
     "fs2hip_pack_spec": "ppppiiip",
+    "fs2hip_zero_tail_rows": "pqpiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -1945,6 +1946,27 @@ def pack_spec(y, lens, packed=None, offsets=None):
     _req(offsets.numel() >= B + 1, f"pack_spec: offsets holds {offsets.numel()} entries, {B + 1} are written")
     _ok(lib().fs2hip_pack_spec(_p(y), _p(lens), _p(packed), _p(offsets), B, Tm, C_, _stream()), "pack_spec")
     return packed, offsets
+
+
+#: launches of ``zero_tail_rows`` so far (a measurement aid: the masks one exact-length forward adds)
+ZERO_TAIL_CALLS = [0]
+
+
+def zero_tail_rows(x, lens, B, T):
+    """Exact-length inference's mask: rows ``t >= clamp(lens[b], 0, T)`` of the dense ``[B, T, ...]`` tensor ``x`` (fp32
+    or bf16, any trailing shape) become zero IN PLACE, by stores -- the tail is never read, so NaN or Inf there is simply
+    overwritten -- and rows below the length are not touched.  ``lens`` [B] int32 stays in GPU memory.  Returns ``x``."""
+    _chk(x, getattr(x, "dtype", torch.float32), "x")  # (its dtype is checked below: two are taken)
+    _chk(lens, torch.int32, "lens")
+    _req(x.dtype in (torch.float32, torch.bfloat16), f"zero_tail_rows: x must be fp32 or bf16, got {x.dtype}")
+    _req(0 < B <= 65535 and T > 0, f"zero_tail_rows: B = {B} (1 to 65535), T = {T} (at least 1)")
+    _req(x.numel() > 0 and x.dim() >= 2 and (tuple(x.shape[:2]) == (B, T) or x.shape[0] == B * T),
+         f"zero_tail_rows: x {tuple(x.shape)} is neither [B, T, ...] nor [B * T, ...] for B = {B}, T = {T}")
+    _req(lens.numel() == B, f"zero_tail_rows: lens has {lens.numel()} entries for {B} utterances")
+    row_bytes = x.numel() // (B * T) * x.element_size()
+    _ok(lib().fs2hip_zero_tail_rows(_p(x), row_bytes, _p(lens), B, T, _stream()), "zero_tail_rows")
+    ZERO_TAIL_CALLS[0] += 1
+    return x
 
 
 # ------------------------------------------------------------------------------------------

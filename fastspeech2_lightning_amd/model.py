@@ -214,8 +214,9 @@ class VarianceAdaptor:
             jobs.append(("duration", x, src_lens))
             c["pred_groups"] += self._run_predictors(jobs, res)
             logd, c["duration"] = res["duration"]
-        elif dur_aligned is not None or teacher_forcing or not inference:
-            # durations come from the batch / the aligner: prediction feeds the loss only
+        elif (dur_aligned is not None or teacher_forcing or not inference) and not self.env.exact:
+            # durations come from the batch / the aligner: prediction feeds the loss only.  (Exact lengths: the predictor
+            # zeroes its input's padded rows in place, so it stays on the stream of that tensor's other readers.)
             with self.env.side(x, src_lens, lane=PRED_LANES["duration"]):
                 logd, c["duration"] = self.duration_predictor.fwd(x, src_lens)
         else:
@@ -643,9 +644,33 @@ class FastSpeech2(_Base):
         return ctx()
 
     # ---- forward (fs2/model.py:153-268) -------------------------------------------------------------
-    def forward(self, batch, control=None, inference=False):
+    def forward(self, batch, control=None, inference=False, exact_lengths=False):
+        """``exact_lengths`` (inference on a model in eval mode only): every utterance's result is what the utterance gives
+        when it is run alone, whatever else is in the batch.  Padded rows are not zero inside the network (biases,
+        LayerNorm's beta, BatchNorm's shift and the variance embeddings fill them) and every operator that mixes along
+        time -- the Conformer's depthwise convolution, the variance predictors' and the PostNet's k-tap convolutions --
+        reads them into an utterance's last frames: with the flag their inputs' padded rows are zeroed on the device
+        first (``hip.zero_tail_rows``, lengths never visit the host).  Without it not one launch changes.  Training and
+        validation keep the reference's definition (BatchNorm statistics and loss denominators include padding)."""
+        if exact_lengths:
+            if not inference:
+                raise ValueError("exact_lengths=True goes with inference=True: training and validation forwards keep the "
+                                 "reference's treatment of padding")
+            if self.training:
+                raise ValueError("exact_lengths=True needs a model in eval mode (model.eval()): in train mode BatchNorm "
+                                 "takes its statistics over the padded batch")
+            if (self.gst is not None and batch.get("mel_lens") is not None
+                    and not torch.is_tensor(batch.get("mel_style_reference"))):
+                raise ValueError("exact_lengths=True: teacher forcing without a style reference runs the GST reference "
+                                 "encoder over the batch's padded target mels (strided convolutions and a GRU over every "
+                                 "frame up to the batch's longest), so the style vector depends on the padding; pass a "
+                                 "mel_style_reference")
         with torch.cuda.device(self.device_):  # kernels launch on the current device: it must be the model's
-            return self._forward(batch, control, inference)
+            self.env.exact = bool(exact_lengths)
+            try:
+                return self._forward(batch, control, inference)
+            finally:
+                self.env.exact = False
 
     def _forward(self, batch, control=None, inference=False):
         H.set_precision(self.precision)
@@ -727,7 +752,7 @@ class FastSpeech2(_Base):
         postnet_output, post_ctx = None, None
         if m.use_postnet:
             with self._prec("postnet"):
-                post, post_ctx = self.postnet.fwd(output)
+                post, post_ctx = self.postnet.fwd(output, tgt_lens)
             postnet_output = H.axpby(output, post)
         if save:
             self._ctx = dict(text=text, enc=enc_ctx, va=va_ctx, dec=dec_ctx, dec_out=y, post=post_ctx, B=B, Ts=Ts, Tm=Tm,
@@ -1235,11 +1260,13 @@ class FastSpeech2(_Base):
             self.optimizer = None  # held the old device record
         return self
 
-    def predict_step(self, batch, batch_idx=0):
+    def predict_step(self, batch, batch_idx=0, exact_lengths=False):
         was = self.training
         self.eval()
-        out = self(batch, inference=True)
-        self.train(was)
+        try:
+            out = self(batch, inference=True, exact_lengths=exact_lengths)
+        finally:
+            self.train(was)
         return out
 
     def configure_optimizers(self):

@@ -39,10 +39,18 @@ class Env:
         self.step_state = step_state
         self.seed = seed
         self._site = 0
+        self.exact = False  # exact-length inference (``FastSpeech2.forward(exact_lengths=True)``): set for one forward
 
     def new_site(self) -> int:
         self._site += 1
         return self._site
+
+    def mask(self, x, lens, B, T):
+        """Exact-length inference: the padded rows of ``x`` [B, T, ...] become zero, in place, in front of an operator that
+        reads neighbours in time (``hip.zero_tail_rows``).  Any other forward: nothing is launched."""
+        if self.exact:
+            H.zero_tail_rows(x, lens, B, T)
+        return x
 
     @property
     def stored(self) -> bool:
@@ -444,7 +452,8 @@ class ConvModule:
         if dims_ok and d == 256:
             S.want_transposed(self.w2)
 
-    def fwd(self, x):
+    def fwd(self, x, lens=None):
+        """``lens`` [B]: the utterances' lengths, read only by exact-length inference (``Env.mask``)."""
         S, env = self.S, self.env
         B, T, _ = x.shape
         stored = env.stored and self.dims_ok
@@ -456,6 +465,9 @@ class ConvModule:
         else:
             h, ln_saved = self.ln.fwd(x)
             g2 = H.linear_fwd(h, S.p(self.w1), S.p(self.b1))
+        # (exact lengths: the pointwise bias made the padded rows of value | gate non-zero, and the k taps would carry them
+        # into the last valid frames.  GLU of a zero row is zero: the fused kernel reads what "same" padding gives it)
+        env.mask(g2, lens, B, T)
         c, parts = H.dwconv_fwd(g2, S.p(self.wd), S.p(self.bd), B, T, glu=True, stats=env.training)
         stats = self.bn.stats(parts, env.training)
         if stored:
@@ -512,7 +524,7 @@ class ConformerLayer:
     def fwd(self, x, lens):
         x, c1 = self.ffn1.fwd(x)
         x, c2 = self.attn.fwd(x, lens)
-        x, c3 = self.conv.fwd(x)
+        x, c3 = self.conv.fwd(x, lens)
         x, c4 = self.ffn2.fwd(x)
         y, c5 = self.final.fwd(x)
         return y, (c1, c2, c3, c4, c5)
@@ -693,6 +705,10 @@ def predictors_fwd(preds, xs, lens):
     B, T, _ = xs[0].shape
     cur, saved = list(xs), [[] for _ in preds]
     for li in range(len(preds[0].layers)):
+        for p, x, l in zip(preds, cur, lens):
+            # exact lengths: the layer's k taps, depthwise or full, must not see padded rows -- the encoder's or the
+            # variance embeddings' in the first layer, LayerNorm's beta in the later ones
+            p.env.mask(x, l, B, T)
         cs = [p._fwd_conv(p.layers[li], x, B, T) for p, x in zip(preds, cur)]
         with H.gemm_group():
             rs = [p._fwd_gemm(p.layers[li], x, c, T) for p, x, c in zip(preds, cur, cs)]
@@ -930,8 +946,11 @@ class PostNet:
             S.add(b, (chans[i + 1],), "id", P.init_bias_for(chans[i] * k))
             self.convs.append((w, b, BatchNorm(S, q + "1.", chans[i + 1]), env.new_site()))
 
-    def fwd(self, x):
-        """bf16 operand storage (``Env.stored``; needs T >= 64 for the weight-gradient form): every 512-channel
+    def fwd(self, x, lens=None):
+        """``lens`` [B]: the utterances' frame counts, read only by exact-length inference (``Env.mask``: the padded rows
+        of every convolution's input -- the mel head's bias, BatchNorm's shift -- are zeroed in front of its k taps).
+
+        bf16 operand storage (``Env.stored``; needs T >= 64 for the weight-gradient form): every 512-channel
         activation exists only as the bf16 tensor the next convolution reads -- written by the BatchNorm + tanh +
         dropout kernel -- and the convolutions read the weights from the bf16 mirror.  The first convolution's input
         (80 mel bins: not whole 64-deep K-tiles per tap) stays on the fp32-operand core."""
@@ -943,6 +962,7 @@ class PostNet:
         stored = env.stored and T >= 64 and self.n_mel % 8 == 0
         saved = []
         for i, (w, b, bn, site) in enumerate(self.convs):
+            env.mask(x, lens, B, T)
             if x.dtype == torch.bfloat16:
                 # a convolution between two bf16-only layers writes a bf16 result as well (what autocast's conv1d
                 # returns): BatchNorm's statistics and both of its passes then read half the bytes.  The last

@@ -10,9 +10,14 @@ asking the GPU again: free inference already reads the frame totals once per bat
 copy event only after the NEXT batch's forward has been enqueued (``depth`` device / pinned buffer pairs in rotation;
 ``depth = 1`` is the fully synchronous form and writes identical files).
 
-A file is what ``forward(inference=True)`` gives for the utterance IN THE BATCH ``data.synthesis_batches`` puts it in
-(padding, and therefore the kernels' tile choice, follow the batch); ``sort=False`` with ``batch_size = 1`` reproduces
-the reference's one-by-one behaviour.
+By default a file is what ``forward(inference=True)`` gives for the utterance IN THE BATCH ``data.synthesis_batches`` puts
+it in: the network's padded rows are not zero and its convolutions read them into an utterance's last frames, so the
+values -- and, through the duration predictor, the frame count -- follow the batch, as they do in the reference;
+``sort=False`` with ``batch_size = 1`` reproduces the reference's one-by-one behaviour.  ``exact_lengths=True``
+(``fs2l synthesize --exact-lengths``) removes the dependence: every file is what the utterance gives when it is synthesized
+alone, whatever the batch size and the sort order (``FastSpeech2.forward(exact_lengths=True)``: the padded rows are zeroed
+on the device in front of every convolution over time).  What is left is rounding: the GEMMs' tile choice follows the
+row count, so two batchings agree to fp32 summation order, not bit for bit.
 """
 from __future__ import annotations
 
@@ -42,11 +47,12 @@ class _Slot:
             self.host = torch.empty(n, dtype=torch.float32).pin_memory()
 
 
-def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2) -> dict:
+def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2,
+               exact_lengths: bool = False) -> dict:
     """Synthesizes every item of ``dataset`` (``data.SynthesisDataset``) and writes the spectrograms through ``writer``
     (``data.PackedSpecWriter``), in input order.  Returns ``{"files": [paths], "utterances": n, "frames": n, "batches": n}``.
     Per batch the host reads the GPU once inside the forward pass (the frame totals; nothing for a teacher-forced batch)
-    and waits once, for the copy event."""
+    and waits once, for the copy event.  ``exact_lengths``: see the module's docstring."""
     if depth < 1:
         raise ValueError("synthesize: depth >= 1")
     if writer is None:
@@ -78,7 +84,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
             slots = [_Slot(device) for _ in range(depth)]
             for i, positions in enumerate(batches):
                 cpu_batch = collate([dataset[j] for j in positions], learn_alignment=learn_alignment, pin_memory=True)
-                out = model(cpu_batch, _copy_control(control), inference=True)
+                out = model(cpu_batch, _copy_control(control), inference=True, exact_lengths=exact_lengths)
                 y = out[model.output_key]
                 B, Tm, C = y.shape
                 if cpu_batch["mel_lens"] is not None:

@@ -571,6 +571,14 @@ int fs2hip_pad_batch(const Fs2PadMember* members, int n, void* stream);
 int fs2hip_pack_spec(const float* y, const int* lens, float* packed, long long* offsets, int B, int Tm, int C,
                      void* stream);
 
+/* Exact-length inference: x is a dense [B][T][row_bytes] activation of any element type, lens [B] in device memory
+ * (clamped to 0..T here).  Every row t >= lens[b] of utterance b becomes all-zero bytes -- 0.0 in fp32 and bf16 alike --
+ * by plain stores: the tail is never read (it may hold NaN or Inf), rows below the length are neither read nor written,
+ * and the work is proportional to the padding.  16-byte stores when row_bytes and x are multiples of 16, else 4-byte,
+ * 2-byte (an odd bf16 column count) or single-byte stores by the same rule.  In place, on the stream, no host
+ * synchronisation.  FS2HIP_EINVAL: a null pointer, a non-positive extent, B > 65535. */
+int fs2hip_zero_tail_rows(void* x, long long row_bytes, const int* lens, int B, int T, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
