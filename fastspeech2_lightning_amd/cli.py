@@ -160,6 +160,10 @@ def build_parser() -> argparse.ArgumentParser:
     sy.add_argument("--exact-lengths", action="store_true",
                     help="every file is what the utterance gives when it is synthesized alone, whatever -b and the sort order are "
                          "(the padded rows are zeroed on the GPU in front of every convolution over time; a few dozen small launches per batch)")
+    sy.add_argument("--return-scores", action="store_true",
+                    help="with -T: also write OUTPUT_DIR/scores-<step>.psv, every utterance's own losses (as if it were scored alone: "
+                         "implies --exact-lengths) and coverage scores, worst first (the reference's return_scores, batched)")
+    sy.add_argument("--scores-only", action="store_true", help="with --return-scores: write the score file and no spectrograms")
     sy.add_argument("--dry-run", action="store_true", help="resolve entries, batches and file names, print them as JSON, touch no GPU")
     return ap
 
@@ -685,7 +689,13 @@ def synthesize_command(args) -> int:
                          "audio into a mel needs the parent toolkit's preprocessor")
     if args.batch_size < 1:
         raise SystemExit("--batch-size must be at least 1")
-    from .data import PackedSpecWriter, SynthesisDataset, synthesis_batches, synthesis_entries
+    if args.return_scores and args.teacher_forcing_directory is None:
+        raise SystemExit("--return-scores needs --teacher-forcing-directory (-T): a loss is taken against the recorded mel and "
+                         "durations, which free synthesis does not have")
+    if args.scores_only and not args.return_scores:
+        raise SystemExit("--scores-only goes with --return-scores")
+    from .data import (PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores, synthesis_batches,
+                       synthesis_entries)
     print(f"Loading checkpoint from {args.model_path}", file=sys.stderr)
     if args.dry_run:
         ckpt = torch.load(args.model_path, map_location="cpu", weights_only=False)
@@ -706,28 +716,41 @@ def synthesize_command(args) -> int:
     dataset = SynthesisDataset(entries, config, model.lang2id, model.speaker2id,
                                teacher_forcing_dir=args.teacher_forcing_directory, style_reference=style)
     sort = not args.no_sort
+    scores = ScoreWriter(args.output_dir, global_step) if args.return_scores else None
     if args.dry_run:
-        print(json.dumps({
+        plan = {
             "checkpoint": str(args.model_path), "global_step": global_step, "output_dir": str(args.output_dir),
             "utterances": len(dataset), "batch_size": args.batch_size, "sort": sort,
-            "exact_lengths": bool(args.exact_lengths),
+            "exact_lengths": bool(args.exact_lengths or args.return_scores),
+            "return_scores": bool(args.return_scores),
             "token_counts": dataset.token_counts, "dropped_symbols": dataset.dropped,
             "batches": synthesis_batches(dataset.token_counts, args.batch_size, sort),
             "entries": [{k: e.get(k) for k in ("basename", "language", "speaker", "duration_control")} for e in entries],
-            "files": synthesis_file_names(dataset, args.output_dir, global_step)}))
+            "files": [] if args.scores_only else synthesis_file_names(dataset, args.output_dir, global_step)}
+        if scores is not None:
+            plan["scores_file"] = str(scores.path)
+            for e, cov in zip(plan["entries"], coverage_scores(dataset.tokens)):
+                e.update(cov)
+        print(json.dumps(plan))
         return 0
     from .config import InferenceControl
     from .synthesis import synthesize
     audio = config.preprocessing.audio
-    writer = PackedSpecWriter(args.output_dir, model.output_key, global_step, audio.input_sampling_rate,
-                              getattr(audio, "spec_type", "mel-librosa"), n_mels=audio.n_mels)
+    writer = None
+    if not args.scores_only:
+        writer = PackedSpecWriter(args.output_dir, model.output_key, global_step, audio.input_sampling_rate,
+                                  getattr(audio, "spec_type", "mel-librosa"), n_mels=audio.n_mels)
     control = InferenceControl(pitch=args.pitch_control, energy=args.energy_control, duration=args.duration_control)
     t0 = time.perf_counter()
-    res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort, exact_lengths=args.exact_lengths)
+    res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort, exact_lengths=args.exact_lengths,
+                     scores=scores)
     torch.cuda.synchronize()
-    print(json.dumps({"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
-                      "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),
-                      "output_dir": str(writer.dir)}), flush=True)
+    report = {"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
+              "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),
+              "output_dir": str(writer.dir if writer is not None else args.output_dir)}
+    if scores is not None:
+        report["scores_file"] = str(scores.close())
+    print(json.dumps(report), flush=True)
     return 0
 
 

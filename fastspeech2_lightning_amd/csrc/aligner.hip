@@ -66,21 +66,23 @@ __global__ __launch_bounds__(256) void attn_dist_kernel(const float* __restrict_
   }
 }
 
-// one wavefront per (b, t1) row
+// one wavefront per (b, t1) row.  own_keys: the log_softmax runs over the utterance's own keys (j < key_lens[b]) instead
+// of all T2 -- what the row gives when the utterance is run alone, where T2 IS its key count (exact-length inference).
 __global__ __launch_bounds__(256) void attn_softmax_kernel(const float* __restrict__ logits, const float* __restrict__ prior,
                                                             const int* __restrict__ key_lens, float* __restrict__ logprob,
-                                                            float* __restrict__ soft, int B, int T1, int T2) {
+                                                            float* __restrict__ soft, int B, int T1, int T2, int own_keys) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= (long long)B * T1) return;
   const int b = (int)(row / T1);
   const int L = key_lens[b];
   const float* x = logits + row * T2;
+  const int Tn = (own_keys && L >= 1 && L < T2) ? L : T2;  // keys the log_softmax normalises over
   float m = NEG_INF;
-  for (int j = lane; j < T2; j += 64) m = fmaxf(m, x[j]);
+  for (int j = lane; j < Tn; j += 64) m = fmaxf(m, x[j]);
   m = fs2_wave_max(m);
   float s = 0.f;
-  for (int j = lane; j < T2; j += 64) s += expf(x[j] - m);
+  for (int j = lane; j < Tn; j += 64) s += expf(x[j] - m);
   const float lse = m + logf(fs2_wave_sum(s));
   float m2 = NEG_INF;
   for (int j = lane; j < T2; j += 64) {
@@ -643,7 +645,16 @@ extern "C" int fs2hip_attn_softmax(const float* logits, const float* prior, cons
                                    float* soft, int B, int T1, int T2, void* stream) {
   if (B <= 0 || T1 <= 0 || T2 <= 0) return FS2HIP_EINVAL;
   const long long rows = (long long)B * T1;
-  attn_softmax_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, S_>>>(logits, prior, key_lens, logprob, soft, B, T1, T2);
+  attn_softmax_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, S_>>>(logits, prior, key_lens, logprob, soft, B, T1, T2, 0);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_attn_softmax_own_keys(const float* logits, const float* prior, const int* key_lens, float* logprob,
+                                            float* soft, int B, int T1, int T2, void* stream) {
+  if (!logits || !prior || !key_lens || !logprob || !soft || B <= 0 || T1 <= 0 || T2 <= 0) return FS2HIP_EINVAL;
+  const long long rows = (long long)B * T1;
+  attn_softmax_kernel<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, S_>>>(logits, prior, key_lens, logprob, soft, B, T1, T2, 1);
   FS2_LAUNCH_CHECK();
   return 0;
 }

@@ -451,6 +451,78 @@ class PackedSpecWriter(SpecWriter):
         return len(self._held) + len(self._chunks)
 
 
+def coverage_scores(token_lists) -> list[dict]:
+    """The two coverage scores the reference attaches to every row when it scores a corpus (fs2/cli/synthesize.py:389-409,
+    there with nltk's ``ngrams``): ``[{"phone_coverage_score": x, "trigram_coverage_score": y}]``, one per entry.
+
+    Counts are taken over the whole list: how often every token occurs, and how often every trigram of consecutive
+    tokens occurs in the entries framed by ``<BOS>`` and ``<EOS>``.  An entry's phone coverage is the sum of 1 / count over
+    its tokens; its trigram coverage is the sum of 1 / count over its trigrams WITHOUT the boundary symbols -- the
+    reference scores it that way -- so an entry of fewer than three tokens gets 0.  Rare tokens and rare contexts weigh
+    more: among utterances with the same loss the file lists the least informative first.
+
+    ``token_lists``: one sequence of hashable tokens per entry -- the ids in ``SynthesisDataset.tokens``.  Symbols the
+    model's table does not hold have already been dropped there (``TextProcessor`` drops them), so they count neither as
+    tokens nor inside a trigram, where the reference counts the filelist's token column as it stands."""
+    from collections import Counter
+    lists = [[t.item() if hasattr(t, "item") else t for t in tokens] for tokens in token_lists]
+    token_counter, trigram_counter = Counter(), Counter()
+    for tokens in lists:
+        token_counter.update(tokens)
+        framed = ["<BOS>"] + tokens + ["<EOS>"]
+        trigram_counter.update(zip(framed, framed[1:], framed[2:]))
+    return [{"phone_coverage_score": sum(1 / token_counter[t] for t in tokens),
+             "trigram_coverage_score": sum(1 / trigram_counter[n] for n in zip(tokens, tokens[1:], tokens[2:]))}
+            for tokens in lists]
+
+
+class ScoreWriter:
+    """The score file of the reference's ``ScorerCallback`` (fs2/prediction_writing_callback.py:138-211):
+    ``<output_dir>/scores-<global_step>.psv``, '|'-separated, one row per dataset entry, worst first -- sorted by
+    ``(-total, trigram_coverage_score)``, entries that tie staying in input order.  ``add`` collects a record (in any
+    order: ``position`` is the entry's place in the input); ``close`` sorts, writes and returns the path.  A loss term
+    the model does not have (``attn_ctc`` without the learned aligner) is an empty field."""
+
+    FIELDS = ("basename", "speaker", "language", "total", "trigram_coverage_score", "duration", "spec", "postnet",
+              "attn_ctc", "attn_bin", "raw_text", "phone_coverage_score")
+
+    def __init__(self, output_dir, global_step: int = 0):
+        self.dir, self.global_step = Path(output_dir), int(global_step)
+        self.records = {}
+
+    @property
+    def path(self) -> Path:
+        return self.dir / f"scores-{self.global_step}.psv"
+
+    def add(self, position: int, record: dict):
+        """``record``: basename, speaker, language, raw_text, the two coverage scores, ``total`` and the loss terms that are
+        present (floats); keys that are not columns of the file (``pitch``, ``energy``) are kept but not written."""
+        position = int(position)
+        if position in self.records:
+            raise ValueError(f"ScoreWriter: position {position} delivered twice")
+        missing = [k for k in ("basename", "total", "trigram_coverage_score") if k not in record]
+        if missing:
+            raise ValueError(f"ScoreWriter: the record of position {position} lacks {missing}")
+        self.records[position] = dict(record)
+
+    def sorted_records(self) -> list[dict]:
+        rows = [self.records[p] for p in sorted(self.records)]
+        rows.sort(key=lambda r: (-r["total"], r["trigram_coverage_score"]))
+        return rows
+
+    def close(self) -> Path:
+        import csv
+        self.dir.mkdir(parents=True, exist_ok=True)
+        with open(self.path, "w", encoding="utf8", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=list(self.FIELDS), delimiter="|", restval="", extrasaction="ignore",
+                               lineterminator="\n")
+            w.writeheader()
+            for r in self.sorted_records():
+                w.writerow({k: (repr(float(v)) if isinstance(v, (int, float)) and not isinstance(v, bool) else v)
+                            for k, v in r.items() if v is not None})
+        return self.path
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # synthesis: text -> inference items -> batches (reference fs2/cli/synthesize.py:136-319, fs2/dataset.py:88-224)
 # ----------------------------------------------------------------------------------------------------------------------

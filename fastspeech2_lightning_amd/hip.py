@@ -129,6 +129,7 @@ SIGNATURES = {
     "fs2hip_sum_slots": "pipp",
     "fs2hip_attn_dist": "pppiiiip",
     "fs2hip_attn_softmax": "pppppiiip",
+    "fs2hip_attn_softmax_own_keys": "pppppiiip",
     "fs2hip_mas": "pippppppiiip",
     "fs2hip_avg_variance": "pppiiip",
     "fs2hip_attn_ctc_loss": "pppppppfpiiip",
@@ -150,6 +151,7 @@ SIGNATURES = {
     "fs2hip_pad_batch": None,  # (const Fs2PadMember*, int, void*): set below
     "fs2hip_pack_spec": "ppppiiip",
     "fs2hip_zero_tail_rows": "pqpiip",
+    "fs2hip_utterance_losses": "pipppiifpfpip",  # (the first: const Fs2ScoreMember*, a ctypes array)
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -1969,6 +1971,82 @@ def zero_tail_rows(x, lens, B, T):
     return x
 
 
+SCORE_MAX_MEMBERS = 8   # FS2_SCORE_MAX_MEMBERS
+SCORE_COLUMNS = ("pitch", "energy", "duration", "spec", "postnet", "attn_ctc", "attn_bin", "total")  # model.LOSS_KEYS + total
+
+
+class ScoreMember(C.Structure):  # mirrors Fs2ScoreMember (include/fs2hip.h)
+    _fields_ = [("pred", C.c_void_p), ("tgt", C.c_void_p), ("tgt_int", C.c_void_p), ("lens", C.c_void_p), ("T", C.c_int),
+                ("C", C.c_int), ("kind", C.c_int), ("weight", C.c_float), ("column", C.c_int), ("pad_", C.c_int)]
+
+
+def utterance_losses(terms, B, *, bin_term=None, ctc_term=None, out=None):
+    """Per-utterance loss scores of a teacher-forced batch: a ``[B, 8]`` fp32 table in GPU memory, columns
+    ``SCORE_COLUMNS``; row b is what the loss gives for utterance b alone, cut to its own lengths
+    (``fs2hip_utterance_losses``: two launches, nothing is read back).
+
+    ``terms``: the mean terms, each ``(column, pred, target, lens, T, C, kind, weight)`` -- ``column`` a name of
+    ``SCORE_COLUMNS`` or its index, ``pred`` fp32 with ``B * T * C`` elements, ``target`` fp32 of that size or int32 (a
+    duration: the loss uses log(target + 1)), ``lens`` [B] int32, ``kind`` "mse" / "mae".  ``bin_term``:
+    ``(soft [B, Tm, Ts], hard_idx [B, Tm] int32, mel_lens [B] int32, weight)``.  ``ctc_term``: ``(nll [B], weight)``, nll
+    as ``attn_ctc_loss(..., nll_out=)`` leaves it.  A column without a term is 0; the total is the last column."""
+    terms = list(terms)
+    _req(isinstance(B, int) and B > 0, f"utterance_losses: B = {B!r} (at least 1)")
+    _req(len(terms) <= SCORE_MAX_MEMBERS, f"utterance_losses: at most {SCORE_MAX_MEMBERS} mean terms, got {len(terms)}")
+    _req(terms or bin_term is not None or ctc_term is not None, "utterance_losses: no term at all")
+    members = (ScoreMember * max(len(terms), 1))()
+    used = set()
+    if bin_term is not None:
+        used.add(SCORE_COLUMNS.index("attn_bin"))
+    if ctc_term is not None:
+        used.add(SCORE_COLUMNS.index("attn_ctc"))
+    device = None
+    for m, (column, pred, target, lens, T, Cc, kind, weight) in zip(members, terms):
+        col = SCORE_COLUMNS.index(column) if isinstance(column, str) else int(column)
+        _req(0 <= col < len(SCORE_COLUMNS) - 1, f"utterance_losses: column {column!r} is not a loss term")
+        _req(col not in used, f"utterance_losses: column {SCORE_COLUMNS[col]!r} is named twice")
+        used.add(col)
+        name = SCORE_COLUMNS[col]
+        _chk(pred, name=f"{name} pred"); _chk(lens, torch.int32, f"{name} lens")
+        _req(isinstance(target, torch.Tensor) and target.dtype in (torch.float32, torch.int32),
+             f"utterance_losses: the {name} target must be an fp32 or int32 tensor")
+        _chk(target, target.dtype, f"{name} target")
+        T, Cc = int(T), int(Cc)
+        _req(T > 0 and Cc > 0, f"utterance_losses: {name}: T = {T}, C = {Cc} (at least 1)")
+        _req(pred.numel() == B * T * Cc and target.numel() == B * T * Cc and lens.numel() == B,
+             f"utterance_losses: {name}: pred {tuple(pred.shape)}, target {tuple(target.shape)}, lens {tuple(lens.shape)} "
+             f"for B = {B}, T = {T}, C = {Cc}")
+        _req(kind in ("mse", "mae"), f"utterance_losses: {name}: kind {kind!r} is neither 'mse' nor 'mae'")
+        m.pred, m.lens, m.T, m.C = _p(pred), _p(lens), T, Cc
+        m.tgt, m.tgt_int = (None, _p(target)) if target.dtype == torch.int32 else (_p(target), None)
+        m.kind, m.weight, m.column = (0 if kind == "mse" else 1), float(weight), col
+        device = pred.device
+    soft = hard_idx = mel_lens = nll = None
+    Tm = Ts = 0
+    bin_w = ctc_w = 0.0
+    if bin_term is not None:
+        soft, hard_idx, mel_lens, bin_w = bin_term
+        _chk(soft, name="soft"); _chk(hard_idx, torch.int32, "hard_idx"); _chk(mel_lens, torch.int32, "mel_lens")
+        _req(soft.dim() == 3 and soft.shape[0] == B and soft.numel() > 0, f"utterance_losses: soft {tuple(soft.shape)} is not "
+             f"[{B}, Tm, Ts]")
+        Tm, Ts = soft.shape[1:]
+        _req(tuple(hard_idx.shape) == (B, Tm) and mel_lens.numel() == B,
+             f"utterance_losses: hard_idx {tuple(hard_idx.shape)} / mel_lens {tuple(mel_lens.shape)} for soft {tuple(soft.shape)}")
+        device = soft.device
+    if ctc_term is not None:
+        nll, ctc_w = ctc_term
+        _chk(nll, name="nll")
+        _req(nll.numel() == B, f"utterance_losses: nll has {nll.numel()} entries for {B} utterances")
+        device = nll.device
+    if out is None:
+        out = torch.empty(B, len(SCORE_COLUMNS), device=device, dtype=torch.float32)
+    _chk(out, name="out")
+    _req(tuple(out.shape) == (B, len(SCORE_COLUMNS)), f"utterance_losses: out is {tuple(out.shape)}, not [{B}, {len(SCORE_COLUMNS)}]")
+    _ok(lib().fs2hip_utterance_losses(members, len(terms), _p(soft), _p(hard_idx), _p(mel_lens), int(Tm), int(Ts),
+                                      float(bin_w), _p(nll), float(ctc_w), _p(out), B, _stream()), "utterance_losses")
+    return out
+
+
 # ------------------------------------------------------------------------------------------
 # optimizer and elementwise
 # ------------------------------------------------------------------------------------------
@@ -2075,13 +2153,15 @@ def attn_dist(q, k):
     return logits
 
 
-def attn_softmax(logits, prior, key_lens):
+def attn_softmax(logits, prior, key_lens, own_keys=False):
+    """``own_keys``: the log_softmax of ``logprob`` runs over each utterance's own keys (``fs2hip_attn_softmax_own_keys``:
+    what the utterance gives alone) instead of all ``T2`` padded ones (the reference's definition on a batch)."""
     _chk(logits, name="logits"); _chk(prior, name="prior"); _chk(key_lens, torch.int32, "key_lens")
     B, T1, T2 = logits.shape
     _req(prior.shape == logits.shape and key_lens.numel() == B, "attn_softmax: shape mismatch")
     logprob, soft = torch.empty_like(logits), torch.empty_like(logits)
-    _ok(lib().fs2hip_attn_softmax(_p(logits), _p(prior), _p(key_lens), _p(logprob), _p(soft), B, T1, T2, _stream()),
-        "attn_softmax")
+    fn = lib().fs2hip_attn_softmax_own_keys if own_keys else lib().fs2hip_attn_softmax
+    _ok(fn(_p(logits), _p(prior), _p(key_lens), _p(logprob), _p(soft), B, T1, T2, _stream()), "attn_softmax")
     return logprob, soft
 
 
@@ -2132,15 +2212,20 @@ def avg_variance(var, cum):
     return out
 
 
-def attn_ctc_loss(logprob, key_lens, query_lens, weight, loss_out, want_grad=True):
+def attn_ctc_loss(logprob, key_lens, query_lens, weight, loss_out, want_grad=True, nll_out=None):
+    """``nll_out`` ([B] fp32, optional) receives the per-utterance losses the batch mean is taken over: utterance b's
+    negative log-likelihood divided by its target length, 0 where it is infinite -- without the weight."""
     _chk(logprob, name="logprob"); _chk(key_lens, torch.int32, "key_lens"); _chk(query_lens, torch.int32, "query_lens")
     _chk(loss_out, name="loss_out")
     B, Tm, Ts = logprob.shape
     _req(key_lens.numel() == B and query_lens.numel() == B and loss_out.numel() == 1, "attn_ctc_loss: shape mismatch")
+    if nll_out is not None:
+        _chk(nll_out, name="nll_out")
+        _req(nll_out.numel() == B, f"attn_ctc_loss: nll_out has {nll_out.numel()} entries for {B} utterances")
     _req(2 * (2 * Ts + 1) * 4 + 16 <= 64 * 1024, "attn_ctc_loss: too many tokens for the on-chip state")
     alpha = torch.empty(B * Tm * (2 * Ts + 1) + B * Tm + B, device=logprob.device, dtype=torch.float32)
     lse = alpha[B * Tm * (2 * Ts + 1):]
-    nll = lse[B * Tm:]
+    nll = lse[B * Tm:] if nll_out is None else nll_out
     d = torch.empty_like(logprob) if want_grad else None
     _ok(lib().fs2hip_attn_ctc_loss(_p(logprob), _p(key_lens), _p(query_lens), _p(alpha), lse.data_ptr(), nll.data_ptr(),
                                    _p(d), weight, _p(loss_out), B, Tm, Ts, _stream()), "attn_ctc_loss")

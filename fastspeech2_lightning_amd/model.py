@@ -1269,6 +1269,66 @@ class FastSpeech2(_Base):
             self.train(was)
         return out
 
+    def utterance_losses(self, output, batch, current_epoch=0, out=None):
+        """Per-utterance loss scores of a teacher-forced inference forward: ``(table, keys)``.  ``table`` is ``[B, 8]`` fp32
+        in GPU memory, columns ``LOSS_KEYS`` and the total last; row b is what ``self.loss`` gives for the batch of ONE
+        made of utterance b cut to its own lengths -- what the reference's ``ScorerCallback``
+        (fs2/prediction_writing_callback.py:138-211) computes at batch size 1.  ``self.loss`` on the batch cannot stand in
+        for it: its means run over the padded box, so it is one number per batch and not the mean of these.  ``keys``: the
+        ``LOSS_KEYS`` that are present, in the order ``FastSpeech2Loss._loss`` produces them (a column that is not is 0);
+        terms, weights, levels and loss kinds are chosen as there.  After an inference forward there are no pitch and energy
+        targets, so those two are absent, as in the reference; the binarisation weight at the default epoch 0 is 0, which
+        is what the reference's scorer sees under ``Trainer.predict``.  ``output`` should come from
+        ``forward(batch, inference=True, exact_lengths=True)``: only then is row b also independent of the rest of the
+        batch upstream of the loss.  Nothing is read back: ``hip.utterance_losses`` (and the CTC recursion with a learned
+        aligner) are enqueued and the table stays on the device.  ``out``: a ``[B, 8]`` fp32 device tensor to fill instead
+        of a fresh one (``synthesize`` hands in a piece of the buffer that leaves the GPU with the spectrograms)."""
+        if self.training:
+            raise ValueError("utterance_losses needs a model in eval mode (model.eval()): scores are an inference result")
+        if output.get("duration_target") is None:
+            raise ValueError("utterance_losses: the output has no duration_target -- a free-inference forward has no "
+                             "targets, so there is nothing to score; run a teacher-forced batch (mel, mel_lens, duration)")
+        with torch.cuda.device(self.device_):
+            self.env.join()
+            batch = self.prepare_batch(batch)
+            cfg, t = self.config.model, self.config.training
+            src_lens, tgt_lens = output["src_lens"], output["tgt_lens"]
+            B = src_lens.numel()
+            Ts, Tm = output["src_mask"].shape[1], output["tgt_mask"].shape[1]
+            terms, keys = [], []
+            for name, w in (("pitch", t.pitch_loss_weight), ("energy", t.energy_loss_weight)):
+                if output.get(f"{name}_target") is None:
+                    continue
+                c = getattr(cfg.variance_predictors, name)
+                phone = c.level.value == "phone"
+                terms.append((name, output[f"{name}_prediction"], output[f"{name}_target"], src_lens if phone else tgt_lens,
+                              Ts if phone else Tm, 1, c.loss.value, w))
+                keys.append(name)
+            terms.append(("duration", output["duration_prediction"], output["duration_target"], src_lens, Ts, 1,
+                          cfg.variance_predictors.duration.loss.value, t.duration_loss_weight))
+            keys.append("duration")
+            mel = batch["mel"]
+            n_mels = mel.shape[-1]
+            terms.append(("spec", output["output"], mel, tgt_lens, Tm, n_mels, cfg.mel_loss.value, t.mel_loss_weight))
+            keys.append("spec")
+            if cfg.use_postnet:
+                terms.append(("postnet", output["postnet_output"], mel, tgt_lens, Tm, n_mels, cfg.mel_loss.value,
+                              t.postnet_loss_weight))
+                keys.append("postnet")
+            bin_term = ctc_term = None
+            if cfg.learn_alignment and output.get("attn_logprob") is not None:
+                lp, soft = output["attn_logprob"], output["attn_soft"]
+                Bm, _, Tmm, Tss = lp.shape
+                nll = torch.empty(Bm, device=lp.device, dtype=torch.float32)
+                H.attn_ctc_loss(lp.view(Bm, Tmm, Tss), batch["src_lens"], batch["mel_lens"], t.attn_ctc_loss_weight,
+                                torch.empty(1, device=lp.device, dtype=torch.float32), want_grad=False, nll_out=nll)
+                ctc_term = (nll, t.attn_ctc_loss_weight)
+                w = min(current_epoch / t.attn_bin_loss_warmup_epochs, 1.0) * t.attn_bin_loss_weight
+                bin_term = (soft.view(Bm, Tmm, Tss), self._hard_idx, batch["mel_lens"], float(w))
+                keys += ["attn_ctc", "attn_bin"]
+            table = H.utterance_losses(terms, B, bin_term=bin_term, ctc_term=ctc_term, out=out)
+        return table, tuple(keys)
+
     def configure_optimizers(self):
         """fs2/model.py:530-549: ``([AdamW], [{"scheduler": NoamLR, "interval": "step"}])`` -- here a
         ``torch.optim.Optimizer`` whose ``step()`` is the fused clip + AdamW + schedule launch over the flat buffers and

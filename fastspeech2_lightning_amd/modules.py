@@ -773,7 +773,9 @@ class Aligner:
         q2 = H.linear_fwd(q1, *self._w("q2"), epi=H.EPI_ACT, act="relu")
         qenc = H.linear_fwd(q2, *self._w("q4"))
         logits = H.attn_dist(qenc, kenc)
-        logprob, soft = H.attn_softmax(logits, prior, src_lens)
+        # (exact lengths: the padded keys' logits are finite -- they must not enter log_softmax's normaliser, or attn_logprob
+        # and with it the CTC score follows the batch's longest text)
+        logprob, soft = H.attn_softmax(logits, prior, src_lens, own_keys=self.env.exact)
         hard, hard_idx, dur = H.mas(soft, src_lens, mel_lens)
         ctx = Ctx(mel=mel, text_emb=text_emb, k1=k1, kenc=kenc, q1=q1, q2=q2, qenc=qenc, logits=logits, soft=soft,
                   hard_idx=hard_idx)

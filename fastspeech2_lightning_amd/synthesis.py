@@ -18,6 +18,13 @@ values -- and, through the duration predictor, the frame count -- follow the bat
 alone, whatever the batch size and the sort order (``FastSpeech2.forward(exact_lengths=True)``: the padded rows are zeroed
 on the device in front of every convolution over time).  What is left is rounding: the GEMMs' tile choice follows the
 row count, so two batchings agree to fp32 summation order, not bit for bit.
+
+``scores`` (a ``data.ScoreWriter``; ``fs2l synthesize -T DIR --return-scores``) adds the reference's ``return_scores``
+(fs2/prediction_writing_callback.py:138-211, there at batch size 1): after each teacher-forced forward
+``FastSpeech2.utterance_losses`` writes the batch's ``[B, 8]`` table of per-utterance losses into the slot's header, behind
+the offsets, so it leaves the GPU inside the copy that carries the spectrograms -- same copy stream, same single wait.
+``exact_lengths`` is forced on: a score must not follow ``-b`` or the sort order.  Without a spectrogram writer (scores
+only) nothing is packed and the copy is the header alone.
 """
 from __future__ import annotations
 
@@ -26,19 +33,21 @@ from typing import Optional
 import torch
 
 from . import hip as H
-from .data import collate, synthesis_batches
+from .data import collate, coverage_scores, synthesis_batches
+from .model import LOSS_KEYS
 
 
 class _Slot:
     """One device buffer + its pinned host twin, both float32: [header | payload].  The header holds the batch's B + 1
-    int64 offsets (2 floats each, rounded up to 4 floats so that the payload starts 16-byte aligned)."""
+    int64 offsets (2 floats each, rounded up to 4 floats so that what follows starts 16-byte aligned) and, when the batch
+    is scored, its [B, 8] table of per-utterance losses."""
 
     def __init__(self, device):
         self.device, self.dev, self.host = device, None, None
 
     @staticmethod
-    def header(B: int) -> int:
-        return -(-2 * (B + 1) // 4) * 4
+    def header(B: int, scored: bool = False) -> int:
+        return -(-2 * (B + 1) // 4) * 4 + (_COLS * B if scored else 0)
 
     def reserve(self, floats: int):
         if self.dev is None or self.dev.numel() < floats:
@@ -47,16 +56,28 @@ class _Slot:
             self.host = torch.empty(n, dtype=torch.float32).pin_memory()
 
 
+_COLS = len(LOSS_KEYS) + 1   # columns of the score table: the loss terms and the total
+
+
 def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2,
-               exact_lengths: bool = False) -> dict:
+               exact_lengths: bool = False, scores=None) -> dict:
     """Synthesizes every item of ``dataset`` (``data.SynthesisDataset``) and writes the spectrograms through ``writer``
     (``data.PackedSpecWriter``), in input order.  Returns ``{"files": [paths], "utterances": n, "frames": n, "batches": n}``.
     Per batch the host reads the GPU once inside the forward pass (the frame totals; nothing for a teacher-forced batch)
-    and waits once, for the copy event.  ``exact_lengths``: see the module's docstring."""
+    and waits once, for the copy event.  ``exact_lengths``: see the module's docstring.  ``scores`` (``data.ScoreWriter``):
+    every entry's per-utterance losses and coverage scores are added to it (the caller closes it); the dataset must be
+    teacher-forced, ``exact_lengths`` is forced on, and ``writer`` may be None (scores only)."""
     if depth < 1:
         raise ValueError("synthesize: depth >= 1")
-    if writer is None:
+    if writer is None and scores is None:
         raise ValueError("synthesize: a PackedSpecWriter is required")
+    scored = scores is not None
+    if scored:
+        if not getattr(dataset, "teacher_forcing", False):
+            raise ValueError("synthesize: scores need a teacher-forced dataset (SynthesisDataset(..., teacher_forcing_dir=...)): "
+                             "free inference has no targets to take a loss against")
+        exact_lengths = True
+        coverage = coverage_scores(dataset.tokens)
     device = model.device_
     n_mels = model.config.preprocessing.audio.n_mels
     learn_alignment = model.config.model.learn_alignment
@@ -64,18 +85,28 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
     was_training = model.training
     model.eval()
     files, frames = [], 0
-    pending = []   # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions)], oldest first
+    pending = []   # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys)], oldest first
 
     def finish(job):
         nonlocal frames
-        slot, event, hdr, total, expect, cpu_batch, positions = job
+        slot, event, hdr, total, expect, cpu_batch, positions, keys = job
         event.synchronize()   # the one wait of this batch
+        if scored:
+            B = len(positions)
+            table = slot.host[hdr - _COLS * B:hdr].view(B, _COLS).tolist()
+            for row, pos, name, speaker, language, text in zip(table, positions, cpu_batch["basename"], cpu_batch["speaker"],
+                                                               cpu_batch["language"], cpu_batch["raw_text"]):
+                rec = dict(basename=name, speaker=speaker, language=language, raw_text=text, total=row[-1], **coverage[pos])
+                rec.update((k, row[LOSS_KEYS.index(k)]) for k in keys)
+                scores.add(pos, rec)
+        frames += expect[-1] // n_mels
+        if writer is None:
+            return
         offsets = slot.host[:2 * len(expect)].view(torch.int64)
         if offsets.tolist() != expect:
             raise RuntimeError("synthesize: the frame counts on the GPU differ from the host's (durations that do not add "
                                f"up to the mel lengths?): offsets {offsets.tolist()} against {expect}")
         files.extend(writer.write_packed(slot.host[hdr:hdr + total], offsets, cpu_batch, positions))
-        frames += total // n_mels
 
     try:
         with torch.cuda.device(device):
@@ -94,10 +125,15 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 expect = [0]
                 for n in lens_host.tolist():
                     expect.append(expect[-1] + int(n) * C)
-                hdr, total = _Slot.header(B), expect[-1]
+                hdr = _Slot.header(B, scored)
+                total = expect[-1] if writer is not None else 0   # (scores only: the header is all that travels)
                 slot = slots[i % depth]   # (its previous batch, i - depth, has been finished: see the drain below)
-                slot.reserve(hdr + B * Tm * C)
-                H.pack_spec(y, out["tgt_lens"], slot.dev[hdr:hdr + B * Tm * C], slot.dev[:2 * (B + 1)].view(torch.int64))
+                slot.reserve(hdr + (B * Tm * C if writer is not None else 0))
+                keys = None
+                if scored:
+                    _, keys = model.utterance_losses(out, cpu_batch, out=slot.dev[hdr - _COLS * B:hdr].view(B, _COLS))
+                if writer is not None:
+                    H.pack_spec(y, out["tgt_lens"], slot.dev[hdr:hdr + B * Tm * C], slot.dev[:2 * (B + 1)].view(torch.int64))
                 packed_ev = torch.cuda.Event()
                 packed_ev.record(main)
                 copy_stream.wait_event(packed_ev)
@@ -106,7 +142,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                     copied_ev = torch.cuda.Event()
                     copied_ev.record(copy_stream)
                 slot.dev.record_stream(copy_stream)
-                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions))
+                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys))
                 # the next batch's forward is enqueued before this batch's copy is waited for: only what exceeds
                 # depth - 1 batches in flight is finished now
                 while len(pending) > depth - 1:
@@ -115,7 +151,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 finish(pending.pop(0))
     finally:
         model.train(was_training)
-    if writer.pending():
+    if writer is not None and writer.pending():
         raise RuntimeError(f"synthesize: {writer.pending()} piece(s) were never written (a text without a last chunk?)")
     return {"files": files, "utterances": len(dataset), "frames": frames, "batches": len(batches)}
 

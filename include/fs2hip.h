@@ -579,6 +579,56 @@ int fs2hip_pack_spec(const float* y, const int* lens, float* packed, long long* 
  * synchronisation.  FS2HIP_EINVAL: a null pointer, a non-positive extent, B > 65535. */
 int fs2hip_zero_tail_rows(void* x, long long row_bytes, const int* lens, int B, int T, void* stream);
 
+/* Per-utterance loss scores of a teacher-forced batch (fs2/prediction_writing_callback.py:138-211 runs the model at batch
+ * size 1 and calls fs2/loss.py:19-126 on every utterance): scores [B][FS2_SCORE_COLUMNS] fp32, dense, every element
+ * written.  Columns: pitch, energy, duration, spec, postnet, attn_ctc, attn_bin, total.  Row b holds what the loss gives
+ * for the batch of ONE made of utterance b cut to its own lengths -- its means run over the utterance's own len_b * C
+ * elements, not over the padded B * T * C box fs2hip_masked_loss divides by.
+ *   members[0 .. n): the mean terms, one per column 0 .. 6, the table passed by value in the kernel argument (a launch plan
+ *     keeps a host copy, as of Fs2PadMember).  pred [B][T][C] fp32; the target is tgt [B][T][C] fp32, or, when tgt_int is
+ *     non-null, log(tgt_int + 1) of an int32 tensor of that shape (durations, fs2/loss.py:81); lens [B] int32 in device
+ *     memory, len_b = clamp(lens[b], 0, T).  scores[b][column] = weight * sum_{t < len_b, c} f(pred - tgt) / (len_b * C),
+ *     f the square (kind 0) or the absolute value (kind 1); 0 when len_b is 0.  Rows at and beyond len_b are never read
+ *     (they may hold NaN).
+ *   soft [B][Tm][Ts], hard_idx [B][Tm] (both or neither), mel_lens [B]: attn_bin = -bin_weight * sum_{t < len_b,
+ *     0 <= hard_idx < Ts} log(max(soft[b][t][hard_idx[b][t]], 1e-12)) / (number of such t), 0 when there is none
+ *     (fs2/attn/attention_loss.py:65-73 on the utterance's own box).
+ *   nll [B] or NULL: attn_ctc = ctc_weight * nll[b], nll being what fs2hip_attn_ctc_loss leaves in nll_ws -- already
+ *     divided by the target length and zeroed where infinite: nn.CTCLoss(zero_infinity=True), mean reduction, batch of one.
+ *   total = the columns 0 .. 6 added in that order in fp32 (fs2hip_sum_slots' order); a column without a term is 0.
+ * Two launches, no atomics, no workspace.  An utterance's elements are added in an order that depends on len_b * C only --
+ * not on B, T, the utterance's place in the batch or the alignment of its base address (16-byte loads are used where the
+ * base allows them, the additions follow the logical element index either way): a row of a batch is bit-equal to the same
+ * data scored with B = 1, T = len_b.
+ * FS2HIP_EINVAL: scores NULL, B <= 0, n < 0 or n > FS2_SCORE_MAX_MEMBERS, a member without pred, lens or a target, with a
+ * non-positive T or C, a kind other than 0 / 1, a column outside 0 .. 6 or one that another member, the binarisation term
+ * (6) or nll (5) also fills; soft without hard_idx or mel_lens or with non-positive Tm / Ts. */
+#define FS2_SCORE_MAX_MEMBERS 8
+#define FS2_SCORE_COLUMNS 8
+typedef struct {
+  const float* pred;
+  const float* tgt;
+  const int* tgt_int; /* non-null: the target is log(tgt_int + 1) and tgt is ignored */
+  const int* lens;
+  int T, C;
+  int kind; /* 0 = squared error, 1 = absolute error */
+  float weight;
+  int column;
+  int pad_;
+} Fs2ScoreMember;
+int fs2hip_utterance_losses(const Fs2ScoreMember* members, int n, const float* soft, const int* hard_idx,
+                            const int* mel_lens, int Tm, int Ts, float bin_weight, const float* nll, float ctc_weight,
+                            float* scores, int B, void* stream);
+
+/* fs2hip_attn_softmax with the log_softmax taken over the utterance's own keys (j < key_lens[b], when 1 <= key_lens[b] < T2)
+ * instead of all T2: row (b, t) of logprob is then what the utterance gives when it is run alone, where T2 is its key
+ * count -- in a padded batch the padded keys' logits are finite and enter the plain form's normaliser, which shifts every
+ * row of logprob by a constant that the CTC loss (its blank logit is a fixed -1) does not forgive.  Exact-length inference
+ * (FastSpeech2.forward(exact_lengths=True)) uses this form.  soft is the same masked softmax (it does not see the shift);
+ * logprob at keys >= key_lens[b] holds the same expression and is not meant to be read.  -22 also for a null pointer. */
+int fs2hip_attn_softmax_own_keys(const float* logits, const float* prior, const int* key_lens, float* logprob,
+                                 float* soft, int B, int T1, int T2, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
