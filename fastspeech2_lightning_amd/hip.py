@@ -293,28 +293,63 @@ class Drop:
 NO_DROP = Drop()
 
 # ------------------------------------------------------------------------------------------
-# workspace (split-K slabs and partial sums): stream-ordered reuse
+# persistent device buffers: workspace (split-K slabs, partial sums), named scratch, split-K counters
 # ------------------------------------------------------------------------------------------
-_WS = {}
+_SCRATCH = {}  # (name, device index, stream handle) -> tensor
+
+
+def persistent_buffer(name, dtype, n, *, zero=False, grow_in_capture=True) -> torch.Tensor:
+    """The grow-only buffer ``name`` of the current device and stream, at least ``n`` elements of ``dtype``: contents
+    are dead between the launches of one call, and calls on one stream are ordered.  ``zero``: zero-filled when
+    (re)allocated.  ``grow_in_capture=False``: refuses to allocate while the stream captures a hipGraph (the buffer
+    would live in the graph's pool and then be used outside it: size it with one eager step first -- ADVICE r4)."""
+    key = (name, _current_device(), _stream())
+    t = _SCRATCH.get(key)
+    if t is None or t.numel() < n:
+        _req(grow_in_capture or not torch.cuda.is_current_stream_capturing(),
+             f"scratch buffer {name!r} must be sized by an eager step before a hipGraph capture")
+        t = _SCRATCH[key] = (torch.zeros if zero else torch.empty)(int(n), device="cuda", dtype=dtype)
+    return t if _REC is None else plan_keep(t)
+
+
+def plan_keep(t: torch.Tensor) -> torch.Tensor:
+    """Notes ``t`` -- a long-lived tensor allocated outside the step (every ``persistent_buffer``; the model's positional
+    table) -- on the launch plan being recorded, if any: the plan stores ``t``'s raw address, so it holds ``t`` for its
+    own lifetime (``StepPlan.borrowed``).  A buffer replaced by a larger one, or dropped by ``release_scratch()``,
+    therefore stays allocated until the last plan that points to it is evicted, cleared or collected.  Worst case, a
+    bound derived from the code and not a measurement: a model keeps ``FS2_PLAN_MAX`` plans, so at most that many
+    superseded generations of each buffer stay alive per model, each smaller than the current one.  Outside a recording
+    this is one ``None`` check."""
+    if _REC is not None:
+        _REC.borrowed[id(t)] = t
+    return t
+
+
+def persistent_buffers() -> dict:
+    """A copy of the registry: (name, device index, stream handle) -> tensor (tests, memory accounting)."""
+    return dict(_SCRATCH)
+
+
+def release_scratch():
+    """Drops every persistent buffer of this process, the split-K counters included (the dS scratch of the attention
+    backward is B*H*T*T floats: 0.9 GB at the configs[4] shape).  They are re-made on demand; recorded launch plans
+    keep the ones they point to, so this is safe while plans exist.  ``FastSpeech2.move_to`` calls this, a caller that
+    switches to much smaller batches may."""
+    _SCRATCH.clear()
 
 
 #: 512 workgroup slots x 128 x 128 partial sums
 HYBRID_WS_FLOATS = 512 * 128 * 128
 
 
-def reserve_workspace(n: int, device) -> torch.Tensor:
-    """Pre-size the scratch buffer (do this before capturing a hipGraph)."""
-    key = (device.index if isinstance(device, torch.device) else device, _stream())  # one scratch buffer per stream
-    ws = _WS.get(key)
-    if ws is None or ws.numel() < n:
-        dev = device if isinstance(device, torch.device) else torch.device("cuda", device)
-        ws = torch.empty(max(n, 1 << 22), device=dev, dtype=torch.float32)
-        _WS[key] = ws
-    return ws
+def reserve_workspace(n: int) -> torch.Tensor:
+    """The current stream's float32 workspace, at least ``n`` floats (pre-size it before capturing a hipGraph)."""
+    return persistent_buffer("ws", torch.float32, max(n, 1 << 22))
 
 
-def _workspace(n: int, device) -> torch.Tensor:
-    return reserve_workspace(n, device)
+def reserve_scratch(name, floats) -> torch.Tensor:
+    """A named float32 scratch buffer that only grows (the dS spill of the attention backwards)."""
+    return persistent_buffer(name, torch.float32, floats, grow_in_capture=False)
 
 
 SPLITK_COUNTERS = 4096  # FS2_SPLITK_COUNTERS
@@ -323,18 +358,13 @@ SPLITK_COUNTERS = 4096  # FS2_SPLITK_COUNTERS
 #: launches get 6 % longer (device-coherent slab stores + the last workgroup's tail)
 SPLITK_IN_KERNEL = os.environ.get("FS2_SPLITK_IN_KERNEL", "0") != "0"
 SPLITK_MAX = int(os.environ.get("FS2_SPLITK_MAX", 16))
-_COUNTERS = {}
 
 
-def splitk_counters(device) -> torch.Tensor:
+def splitk_counters(device=None) -> torch.Tensor:
     """The per-output-tile arrival counters of the current stream's split-K GEMMs (zero between launches: the
-    workgroup that finishes a tile re-arms its counter).  Allocate before capturing a hipGraph."""
-    key = (device.index if isinstance(device, torch.device) else device, _stream())
-    c = _COUNTERS.get(key)
-    if c is None:
-        dev = device if isinstance(device, torch.device) else torch.device("cuda", device)
-        c = _COUNTERS[key] = torch.zeros(SPLITK_COUNTERS, device=dev, dtype=torch.int32)
-    return c
+    workgroup that finishes a tile re-arms its counter).  Allocate before capturing a hipGraph.  (``device``: what
+    callers used to pass; the counters are the current device's, as every launch is.)"""
+    return persistent_buffer("splitk_counters", torch.int32, SPLITK_COUNTERS, zero=True)
 
 
 # ------------------------------------------------------------------------------------------
@@ -641,7 +671,7 @@ def _gemm(_algorithmic=True, **kw):
     for k, v in kw.items():
         setattr(a, k, v)
     if not a.workspace:  # scratch for the split-tail tiles (13-15): at most one slab of partial sums per workgroup slot
-        ws = _workspace(HYBRID_WS_FLOATS, _current_device())
+        ws = reserve_workspace(HYBRID_WS_FLOATS)
         a.workspace, a.workspace_floats = _p(ws), ws.numel()
     if not a.operand_bf16:  # (3 / 4 = bf16 operands in memory: set by the caller that passes bf16 tensors)
         a.operand_bf16 = int(GEMM_BF16) if _algorithmic else 0
@@ -1072,12 +1102,12 @@ def _linear_bwd_weight(dy, x, out, *, taps=1, T=0, n_valid=None, bias_grad=None)
         _defer_reduction(part, S, N, N, bias_grad, N, None)
     if S > 1:
         n = taps * N * K
-        ws = _workspace(S * n, dy.device)
+        ws = reserve_workspace(S * n)
         kw["workspace"] = _p(ws)
         kw["workspace_floats"] = ws.numel()
         in_kernel = (not stored) and SPLITK_IN_KERNEL and taps * ((N + 63) // 64) * ((K + 63) // 64) <= SPLITK_COUNTERS
         if in_kernel:  # the last workgroup of every output tile sums the slabs: no second launch
-            kw["counters"] = _p(splitk_counters(dy.device))
+            kw["counters"] = _p(splitk_counters())
         defer = _DEFER_SLABS and not in_kernel
         if defer or _GROUP is not None:
             # a buffer of its own: summed with every other pending split at the next flush_grad_reductions() / not shared
@@ -1157,7 +1187,7 @@ def colsum(x, out):
     M, N = _rows(x), x.shape[-1]
     _req(out.numel() == N, "colsum: bad output size")
     gy = lib().fs2hip_colsum_rows(M)
-    ws = _workspace(gy * N, x.device)
+    ws = reserve_workspace(gy * N)
     _ok(lib().fs2hip_colsum(_p(x), N, M, N, _p(ws), _p(out), _stream()), "colsum")
     return out
 
@@ -1356,7 +1386,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dx_add=None, defer=Fa
                                        None, None, M, Cc, _stream()), "layernorm_bwd")
         _defer_reduction(part, nblk, 2 * Cc, 2 * Cc, dgamma, Cc, dbeta)
         return dx
-    ws = _workspace(nblk * 2 * Cc, x.device)
+    ws = reserve_workspace(nblk * 2 * Cc)
     _ok(lib().fs2hip_layernorm_bwd(_p(dy), _p(x), _p(gamma), _p(mean), _p(rstd), _p(dx_add), _p(dx), _p(ws),
                                    _p(dgamma), _p(dbeta), M, Cc, _stream()), "layernorm_bwd")
     return dx
@@ -1431,31 +1461,6 @@ def attention_fwd(qkv, lens, B, T, H, drop: Drop = NO_DROP, save_scores=False):
 
 #: FS2_ATTN_SPILL=0: the fp32 attention backward recomputes S and dP in both gradient kernels (the round-2 structure)
 ATTN_SPILL = os.environ.get("FS2_ATTN_SPILL", "1") != "0"
-_SCRATCH = {}
-
-
-def reserve_scratch(name, floats):
-    """A float32 scratch buffer per (name, device, stream) that only grows: contents are dead between the launches of one
-    call, and calls on one stream are ordered."""
-    key = (name, _current_device(), _stream())
-    t = _SCRATCH.get(key)
-    if t is None or t.numel() < floats:
-        # (a buffer first allocated while a hipGraph is captured would live in the graph's pool and then be used outside
-        # it: size the scratch with one eager step before capturing -- ADVICE r4)
-        _req(not torch.cuda.is_current_stream_capturing(),
-             f"scratch buffer {name!r} must be sized by an eager step before a hipGraph capture")
-        t = _SCRATCH[key] = torch.empty(int(floats), device="cuda", dtype=torch.float32)
-    return t
-
-
-def release_scratch():
-    """Drops every grow-only scratch / workspace buffer of this process (the dS scratch of the attention backward is
-    B*H*T*T floats: 0.9 GB at the configs[4] shape).  They are re-made on demand; ``FastSpeech2.move_to`` calls this, a
-    caller that switches to much smaller batches may."""
-    _SCRATCH.clear()
-    _WS.clear()
-
-
 def attention_bwd(qkv, lens, o, dout, lse, B, T, H, drop: Drop = NO_DROP, scores=None):
     """The backward pass of ``attention_fwd``.  At a padded head dimension qkv, o and dout are zero-padded again (o's pad
     columns are the forward's exact zeros) and dqkv is cut back to HD columns per head."""
@@ -1605,7 +1610,7 @@ def dwconv_bwd(dy, x, w, dw, dbias, B, T, *, glu=False, out_dtype=torch.float32)
                                       None, None, B, T, Cc, K, int(glu), _stream()), "dwconv_bwd")
         _defer_reduction(part, nblk, stride, stride, dw, K * Cc, dbias)
         return dx
-    ws = _workspace(nblk * stride, x.device)
+    ws = reserve_workspace(nblk * stride)
     _ok(lib().fs2hip_dwconv_bwd_b(_p(dy), _p(x), ldx, _p(w), _p(dx), int(out_dtype == torch.bfloat16) | (2 if xb else 0), _p(ws), _p(dw),
                                   _p(dbias), B, T, Cc, K, int(glu), _stream()), "dwconv_bwd")
     return dx
@@ -1670,7 +1675,7 @@ def bn_act_bwd(dout, y, stats, dgamma, dbeta, act=None, drop: Drop = NO_DROP, tr
     _req(dout.shape == y.shape and stats.numel() == 5 * Cc and dgamma.numel() == Cc and dbeta.numel() == Cc,
          "bn_act_bwd: shape mismatch")
     nparts = lib().fs2hip_colstats_parts(M)
-    ws = _workspace(nparts * 2 * Cc + 2 * Cc, y.device)
+    ws = reserve_workspace(nparts * 2 * Cc + 2 * Cc)
     coef_ptr = ws.data_ptr() + 4 * nparts * 2 * Cc
     dy = None if bf16_only else torch.empty(y.shape, device=y.device, dtype=torch.float32)
     dy_b = torch.empty(y.shape, device=y.device, dtype=torch.bfloat16) if (bf16_copy or bf16_only) else None
@@ -1812,7 +1817,7 @@ def rowdot_bwd(dout, x, w, lens, dw, dbias, B, T):
          "rowdot_bwd: shape mismatch")
     dx = torch.empty_like(x)
     nblk = lib().fs2hip_rowdot_blocks(B * T)
-    ws = _workspace(nblk * (Cc + 1), x.device)
+    ws = reserve_workspace(nblk * (Cc + 1))
     _ok(lib().fs2hip_rowdot_bwd(_p(dout), _p(x), _p(w), _p(lens), _p(dx), _p(ws), _p(dw), _p(dbias), B * T, T, Cc,
                                 _stream()), "rowdot_bwd")
     return dx
@@ -1830,7 +1835,7 @@ def masked_loss(pred, target, lens, B, T, Cc, *, kind="mse", weight=1.0, loss_ou
     else:
         tf = _chk(target, name="target")
     dpred = torch.empty_like(pred) if want_grad else None
-    ws = _workspace(1024, pred.device)
+    ws = reserve_workspace(1024)
     _ok(lib().fs2hip_masked_loss(_p(pred), _p(tf), _p(ti), _p(lens), B, T, Cc, 0 if kind == "mse" else 1, weight,
                                  _p(dpred), _p(ws), _p(loss_out), _stream()), "masked_loss")
     return dpred
@@ -2073,7 +2078,7 @@ def step_advance(state, base_lr, warmup, beta1, beta2):
 
 def grad_clip_coef(grad, max_norm, grad_scale, state):
     _chk(grad, name="grad"); _chk(state, torch.int64, "state")
-    ws = _workspace(1024, grad.device)
+    ws = reserve_workspace(1024)
     _ok(lib().fs2hip_grad_clip_coef(_p(grad), grad.numel(), float(max_norm), float(grad_scale), _p(ws), _p(state),
                                     _stream()), "grad_clip_coef")
 
@@ -2237,7 +2242,7 @@ def attn_bin_loss(soft, hard_idx, weight, loss_out):
     _chk(soft, name="soft"); _chk(hard_idx, torch.int32, "hard_idx"); _chk(loss_out, name="loss_out")
     B, Tm, Ts = soft.shape
     _req(hard_idx.shape == (B, Tm) and loss_out.numel() == 1, "attn_bin_loss: shape mismatch")
-    ws = _workspace(1024, soft.device)
+    ws = reserve_workspace(1024)
     coef = torch.empty(1, device=soft.device, dtype=torch.float32)
     _ok(lib().fs2hip_attn_bin_loss(_p(soft), _p(hard_idx), _p(ws), weight, _p(loss_out), _p(coef), B, Tm, Ts, _stream()),
         "attn_bin_loss")
@@ -2336,7 +2341,7 @@ def conv2d_s2_bwd(dy, x, w, dw, need_dx=True):
         linear_bwd_weight(col, dy.view(M, Cout), dw, n_valid=9)
         return None
     parts = lib().fs2hip_conv2d_s2_wgrad_parts(B, Hh, Ww)
-    ws = _workspace(parts * w.numel(), x.device)
+    ws = reserve_workspace(parts * w.numel())
     _ok(lib().fs2hip_conv2d_s2_bwd_weight(_p(x), _p(dy), _p(ws), _p(dw), B, Hh, Ww, Cin, Cout, _stream()), "conv2d_s2_bwd_weight")
     if not need_dx:
         return None

@@ -592,7 +592,7 @@ class FastSpeech2(_Base):
             d = self.config.model.encoder.input_dim
             tab = H.posenc_table(self.store.b("position_embedding.inv_freq"), max(T, 256), d)
             self._tables["tab"] = tab
-        return tab
+        return H.plan_keep(tab)  # (a recorded launch plan reads it by address: the plan holds it)
 
     def _dev(self, t, dtype=None):
         if t is None or not torch.is_tensor(t):

@@ -12,7 +12,11 @@ device memory).  So:
   entry-point call -- op id, argument slots, main or side stream -- to a ``Recorder``; ``modules.Env`` reports its fork /
   join events; host-side hand-offs that must happen at a fixed place in the sequence (a gradient bucket's all-reduce,
   ``parallel.GradSync``) are recorded as callbacks that split the plan into segments.  The step's allocations come from
-  a ``torch.cuda.MemPool`` of the plan's own, so the recorded addresses stay reserved for it;
+  a ``torch.cuda.MemPool`` of the plan's own, so the recorded addresses stay reserved for it.  The long-lived buffers
+  a step uses from OUTSIDE that pool -- ``hip.persistent_buffer`` (workspace, dS scratch, split-K counters) and the
+  model's positional table, which are replaced when a larger batch arrives -- are noted on the recorder as they are
+  handed out (``hip.plan_keep``) and held by the plan (``StepPlan.borrowed``): a superseded or released buffer stays
+  allocated until the last plan that points to it is gone, so ``hip.release_scratch()`` is safe while plans exist;
 * every later step of that geometry copies the batch into the recorded input tensors (a batch of a length bucket:
   copied AND padded to the bucket's geometry by one ``fs2hip_pad_batch`` launch, ``StepPlan.feed_padded``) and calls
   ``fs2hip_plan_replay`` (csrc/plan.hip) once per segment: the host cost of the step is the ~5 us ``hipLaunchKernel``
@@ -107,6 +111,7 @@ class Recorder:
         self.streams = [int(main_stream or 0)]   # raw handles: [0] the main stream, then side streams as they appear
         self.cmds = []             # (op, stream index, [slot values])
         self.keep = []             # host copies of struct arguments (addresses are in the slots)
+        self.borrowed = {}         # id -> long-lived device tensor from outside the plan's pool (hip.plan_keep)
         self.n_events = 0
         self.segments = []         # [(end index in cmds, callback, stream index the callback runs under)]
         self.host_ops = []         # callables re-run after every replay (order-free host / ATen work)
@@ -210,6 +215,7 @@ class StepPlan:
                 c.a[j] = v
         self.n = n
         self.keep = rec.keep
+        self.borrowed = tuple(rec.borrowed.values())   # held so that the recorded addresses stay allocated
         self.pool = pool
         self.inputs = inputs          # key -> the device tensor the recorded step read
         self.result = result

@@ -130,7 +130,7 @@ def test_bf16_storage_backward_with_spilled_ds_equals_the_recomputing_one(H, B, 
         monkeypatch.setattr(H, "ATTN_SPILL_B", False)
         want = H.attention_bwd_b(qkv, lens_t, o, dout, lse, B, T, Hh, drop).float()
         monkeypatch.setattr(H, "ATTN_SPILL_B", True)
-        H._SCRATCH.clear()
+        H.release_scratch()
         got = H.attention_bwd_b(qkv, lens_t, o, dout, lse, B, T, Hh, drop).float()
         assert torch.isfinite(got).all()
         assert torch.equal(got[..., D:], want[..., D:]), "dK / dV changed"

@@ -184,7 +184,7 @@ def test_spilled_ds_backward_equals_the_recomputing_backward(H, B, T, Hh, hd, le
         monkeypatch.setattr(H, "ATTN_SPILL", False)
         want = H.attention_bwd(qkv, lens_t, o, dout, lse, B, T, Hh, drop)
         monkeypatch.setattr(H, "ATTN_SPILL", True)
-        H._SCRATCH.clear()
+        H.release_scratch()
         got = H.attention_bwd(qkv, lens_t, o, dout, lse, B, T, Hh, drop)
         assert torch.isfinite(got).all()
         assert torch.equal(got[..., D:], want[..., D:]), "dK / dV changed"

@@ -3,6 +3,9 @@ enqueues exactly what the eager step enqueues: two models from one seed, one wit
 batches -- same geometry, fresh contents every step -- must agree BIT FOR BIT on every loss term of every step, and
 after the run on every weight, Adam moment, BatchNorm buffer and counter.  Dropout is on (masks advance through the
 device step counter), so a replay that missed a launch, a fill or an event would show at once."""
+import gc
+import weakref
+
 import pytest
 import torch
 
@@ -42,9 +45,10 @@ def build(precision="32-true", plan=True, **cfg):
 def batches(config, n, learn_alignment=False, seed=21, **kw):
     """n batches of ONE geometry with different contents."""
     out = []
+    kw = dict(dict(ts_lo=6, ts_hi=12, dur_hi=4), **kw)
     for i in range(n):
-        b = synthetic_batch(B=4, ts_lo=6, ts_hi=12, n_symbols=C.N_SYMBOLS, n_mels=config.preprocessing.audio.n_mels,
-                            seed=seed, content_seed=100 + i, dur_hi=4, learn_alignment=learn_alignment, **kw)
+        b = synthetic_batch(B=4, n_symbols=C.N_SYMBOLS, n_mels=config.preprocessing.audio.n_mels,
+                            seed=seed, content_seed=100 + i, learn_alignment=learn_alignment, **kw)
         b["speaker_id"] = torch.arange(4, dtype=torch.int32) % 4
         b["language_id"] = torch.arange(4, dtype=torch.int32) % 4
         b["basename"] = [f"utt{i}_{j}" for j in range(4)]
@@ -61,6 +65,9 @@ def run(model, opt, bs):
         opt.step()
     torch.cuda.synchronize()
     return rows
+
+
+OUTPUT_KEYS = ("output", "postnet_output", "duration_prediction", "pitch_prediction", "energy_prediction", "tgt_mask")
 
 
 def assert_same_state(a, b):
@@ -92,7 +99,7 @@ def test_replayed_steps_equal_eager_steps_bit_for_bit(variant):
     for i, (w, g) in enumerate(zip(want, got)):
         assert torch.isfinite(w).all() and torch.equal(w, g), (variant, i, w.tolist(), g.tolist())
     assert_same_state(eager, planned)
-    for k in ("output", "postnet_output", "duration_prediction", "pitch_prediction", "energy_prediction", "tgt_mask"):
+    for k in OUTPUT_KEYS:
         assert torch.equal(eager.last_output[k], planned.last_output[k]), k
     plan = next(iter(planned.plans.plans.values()))
     assert plan.launches > 100 and plan.n_events > 4
@@ -112,6 +119,100 @@ def test_two_geometries_alternate_between_their_plans_and_an_unseen_one_runs_eag
     for i, (w, g) in enumerate(zip(want, got)):
         assert torch.equal(w, g), i
     assert_same_state(eager, planned)
+
+
+WIDE = dict(gst=True, multispeaker=True, n_mels=80)   # d = 256, two heads of 128
+
+
+def step(model, opt, b):
+    with torch.no_grad():
+        model.training_step(b)
+    row = model._loss_slots.clone()
+    opt.step()
+    return row
+
+
+def poison_of(sizes):
+    """One fresh float tensor per byte size (NaN under this file's allocation poison): takes over a freed block of
+    exactly that size, if there is one."""
+    return [torch.empty(n // 4, device="cuda") for n in sizes]
+
+
+@pytest.mark.parametrize("precision", ["32-true", "bf16-mixed"])
+def test_a_plan_keeps_the_buffers_a_longer_batch_replaces(precision):
+    """Geometry A is recorded, then a longer batch G runs eagerly and replaces the positional table (more than its 256
+    rows) and the attention backward's dS scratch (``hip.persistent_buffer``).  A's plan recorded the OLD addresses: it
+    holds those tensors (``StepPlan.borrowed``), so they are not free for the NaN-filled tensors allocated here at
+    exactly their sizes, and A's replays after G still equal the eager model's bit for bit.  When the plan goes, the
+    superseded tensors go with it.  (The model is the file's d = 256 one: its head dimension, 128, is one the spilled-dS
+    backwards take; at ``small_config``'s 16 there is no dS scratch and only the table would grow.)"""
+    eager, opt_e, config = build(precision, plan=False, **WIDE)
+    planned, opt_p, _ = build(precision, plan=True, **WIDE)
+    a = batches(config, 5)
+    g = batches(config, 1, seed=22, ts_lo=60, ts_hi=100, dur_hi=6)[0]
+    assert g["max_mel_len"] > 256 and g["max_src_len"] > a[0]["max_src_len"]
+    order = [a[0], a[1], a[2], g, a[3], a[4]]
+    want = run(eager, opt_e, order)
+    H.release_scratch()   # (the eager model's G sized the shared buffers: A starts from fresh, small ones again)
+    got = [step(planned, opt_p, b) for b in order[:3]]   # eager, recorded, replayed
+    (plan,) = planned.plans.plans.values()
+    refs = [weakref.ref(t) for t in plan.borrowed]
+    tab_ref = weakref.ref(planned._tables["tab"])
+    assert any(r() is tab_ref() for r in refs)
+    current = {k: weakref.ref(t) for k, t in H.persistent_buffers().items()}
+    sizes = [r().numel() * r().element_size() for r in refs]
+    ptrs = [r().data_ptr() for r in refs]
+
+    got.append(step(planned, opt_p, g))
+    torch.cuda.synchronize()
+    after = H.persistent_buffers()
+    assert planned._tables["tab"] is not tab_ref() and planned._tables["tab"].shape[0] > 256
+    grown = [k for k, r in current.items() if after[k] is not r()]
+    assert grown, "G replaced no registry buffer"
+    assert all(r() is not None for r in refs)
+    assert {id(r()) for r in refs} == {id(t) for t in plan.borrowed} and [r().data_ptr() for r in refs] == ptrs
+    live = [planned._tables["tab"], *after.values()]
+    superseded = [i for i, r in enumerate(refs) if not any(r() is t for t in live)]   # (the old table and what grew)
+    assert len(superseded) == 1 + len(grown)
+    poison = poison_of(sizes)
+    assert all(torch.isnan(p).all() for p in poison) and not set(ptrs) & {p.data_ptr() for p in poison}
+
+    got += [step(planned, opt_p, b) for b in order[4:]]
+    torch.cuda.synchronize()
+    assert (planned.plans.recorded, planned.plans.replayed, planned.plans.eager) == (1, 3, 2)
+    for i, (w, v) in enumerate(zip(want, got)):
+        assert torch.isfinite(w).all() and torch.equal(w, v), (precision, i, w.tolist(), v.tolist())
+    assert_same_state(eager, planned)
+    for k in OUTPUT_KEYS:
+        assert torch.equal(eager.last_output[k], planned.last_output[k]), k
+
+    planned.plans.clear()
+    del plan
+    gc.collect()
+    assert all((r() is None) == (i in superseded) for i, r in enumerate(refs))
+    assert planned._tables["tab"] is live[0] and all(H.persistent_buffers()[k] is t for k, t in after.items())
+    del poison
+
+
+@pytest.mark.parametrize("precision", ["32-true", "bf16-mixed"])
+def test_release_scratch_between_replays_changes_nothing(precision):
+    """``hip.release_scratch()`` while a plan exists: the plan holds the buffers it recorded, the registry starts over."""
+    eager, opt_e, config = build(precision, plan=False, **WIDE)
+    planned, opt_p, _ = build(precision, plan=True, **WIDE)
+    bs = batches(config, 4)
+    want = run(eager, opt_e, bs)
+    got = [step(planned, opt_p, b) for b in bs[:3]]
+    (plan,) = planned.plans.plans.values()
+    H.release_scratch()
+    assert not H.persistent_buffers()
+    poison = poison_of(t.numel() * t.element_size() for t in plan.borrowed)
+    got.append(step(planned, opt_p, bs[3]))
+    torch.cuda.synchronize()
+    assert (planned.plans.recorded, planned.plans.replayed, planned.plans.eager) == (1, 2, 1)
+    for i, (w, v) in enumerate(zip(want, got)):
+        assert torch.isfinite(w).all() and torch.equal(w, v), (precision, i, w.tolist(), v.tolist())
+    assert_same_state(eager, planned)
+    del poison
 
 
 def test_recorded_outputs_are_rewritten_in_place_and_host_batches_are_fed():
