@@ -126,6 +126,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="length-bucketed training batches: utterances of similar mel length share a batch, and every batch is "
                          "padded (on the GPU) to its bucket's geometry, so that steps replay their launch plans on ragged "
                          "data.  N = number of buckets (default: the launch-plan limit FS2_PLAN_MAX).  Off by default")
+    tr.add_argument("--compute-attn-prior", action="store_true",
+                    help="a model that learns its alignment: open no attn/*-attn-prior.pt file and compute the attention prior on the GPU "
+                         "from each batch's lengths (fs2hip_attn_prior; this project's beta-binomial definition).  Ignored when "
+                         "model.learn_alignment is false")
     tr.add_argument("--dry-run", action="store_true", help="resolve config, filelists, look-up tables and the run directory, print the plan, touch no GPU "
                                                              "(with --bucket-lengths: also reads every item's lengths once and writes the cache "
                                                              "<run dir>/lengths.json, then prints the bucket table)")
@@ -136,6 +140,7 @@ def build_parser() -> argparse.ArgumentParser:
     bm.add_argument("--warmup-reps", type=int, default=10)
     bm.add_argument("--repetitions", type=int, default=300)
     bm.add_argument("--precision", default="32-true", choices=["32-true", "32-split", "bf16-mixed"])
+    bm.add_argument("--compute-attn-prior", action="store_true", help="as for train: the batch carries no prior, the forward computes it")
     sy = sub.add_parser("synthesize", help="Given some text and a trained model, write predicted spectrograms (reference fs2/cli/synthesize.py)")
     sy.add_argument("model_path", type=Path, help="a trained text-to-spec checkpoint")
     sy.add_argument("-t", "--text", dest="texts", action="append", default=[], help="some text to synthesize; can be repeated")
@@ -164,6 +169,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with -T: also write OUTPUT_DIR/scores-<step>.psv, every utterance's own losses (as if it were scored alone: "
                          "implies --exact-lengths) and coverage scores, worst first (the reference's return_scores, batched)")
     sy.add_argument("--scores-only", action="store_true", help="with --return-scores: write the score file and no spectrograms")
+    sy.add_argument("--compute-attn-prior", action="store_true",
+                    help="with -T, " + "a model that learns its alignment: open no attn/*-attn-prior.pt file and compute the attention prior on the GPU "
+                         "from each batch's lengths (fs2hip_attn_prior; this project's beta-binomial definition).  Ignored when "
+                         "model.learn_alignment is false")
     sy.add_argument("--dry-run", action="store_true", help="resolve entries, batches and file names, print them as JSON, touch no GPU")
     return ap
 
@@ -208,6 +217,16 @@ def plan(args) -> dict:
                 val_rows=val_rows, run_dir=out, ckpt_dir=ckpt_dir, resume=resume,
                 max_steps=args.max_steps if args.max_steps is not None else t.max_steps,
                 max_epochs=args.max_epochs if args.max_epochs is not None else t.max_epochs)
+
+
+def attn_prior_mode(args, config) -> dict:
+    """``--compute-attn-prior`` resolved against the model: what the datasets are built with (``attn_prior``) and what a dry
+    run reports -- with a note when the flag was given to a model that has no aligner to feed."""
+    asked = bool(getattr(args, "compute_attn_prior", False))
+    if asked and not config.model.learn_alignment:
+        return {"attn_prior": "files", "attn_prior_note": "--compute-attn-prior ignored: model.learn_alignment is false "
+                                                          "(the batch carries durations, not a prior)"}
+    return {"attn_prior": "computed" if asked else "files"}
 
 
 def bucket_count(args) -> Optional[int]:
@@ -288,8 +307,9 @@ class Trainer:
         self._tiles_shared = world == 1
         self.n_buckets = bucket_count(args)
         cfg = self.model.config
-        self.train_set = FeatureDataset(p["train_rows"], cfg, self.model.lang2id, self.model.speaker2id)
-        self.val_set = FeatureDataset(p["val_rows"], cfg, self.model.lang2id, self.model.speaker2id)
+        prior = attn_prior_mode(args, cfg)["attn_prior"]
+        self.train_set = FeatureDataset(p["train_rows"], cfg, self.model.lang2id, self.model.speaker2id, attn_prior=prior)
+        self.val_set = FeatureDataset(p["val_rows"], cfg, self.model.lang2id, self.model.speaker2id, attn_prior=prior)
         self.H = H
         self.metrics = None
         if rank == 0:
@@ -572,6 +592,7 @@ def train(args, argv) -> int:
             "lang2id": p["lang2id"], "speaker2id": p["speaker2id"], "batch_size": p["config"].training.batch_size,
             "max_steps": p["max_steps"], "max_epochs": p["max_epochs"], "monitor": MONITOR,
             "gradient_clip_val": GRADIENT_CLIP_VAL, "learn_alignment": p["config"].model.learn_alignment,
+            **attn_prior_mode(args, p["config"]),
             "stats": sorted(p["stats"])}))
         return 0
     world = int(os.environ.get("WORLD_SIZE", 0))
@@ -626,7 +647,8 @@ def benchmark(args) -> int:
     config = p["config"]
     model = FastSpeech2(config, Stats(**p["stats"]), p["lang2id"], p["speaker2id"], precision=args.precision)
     model.eval()
-    ds = FeatureDataset(p["train_rows"], config, p["lang2id"], p["speaker2id"])
+    ds = FeatureDataset(p["train_rows"], config, p["lang2id"], p["speaker2id"],
+                        attn_prior=attn_prior_mode(args, config)["attn_prior"])
     n = min(config.training.batch_size, len(ds))
     batch = model.prepare_batch(collate([ds[i] for i in range(n)], learn_alignment=config.model.learn_alignment))
     inference = args.benchmark_type == "inference"
@@ -714,7 +736,8 @@ def synthesize_command(args) -> int:
     entries = synthesis_entries(args.texts, args.filelist, args.language, args.speaker, args.duration_control, model,
                                 args.text_representation)
     dataset = SynthesisDataset(entries, config, model.lang2id, model.speaker2id,
-                               teacher_forcing_dir=args.teacher_forcing_directory, style_reference=style)
+                               teacher_forcing_dir=args.teacher_forcing_directory, style_reference=style,
+                               attn_prior=attn_prior_mode(args, config)["attn_prior"])
     sort = not args.no_sort
     scores = ScoreWriter(args.output_dir, global_step) if args.return_scores else None
     if args.dry_run:
@@ -722,7 +745,7 @@ def synthesize_command(args) -> int:
             "checkpoint": str(args.model_path), "global_step": global_step, "output_dir": str(args.output_dir),
             "utterances": len(dataset), "batch_size": args.batch_size, "sort": sort,
             "exact_lengths": bool(args.exact_lengths or args.return_scores),
-            "return_scores": bool(args.return_scores),
+            "return_scores": bool(args.return_scores), **attn_prior_mode(args, config),
             "token_counts": dataset.token_counts, "dropped_symbols": dataset.dropped,
             "batches": synthesis_batches(dataset.token_counts, args.batch_size, sort),
             "entries": [{k: e.get(k) for k in ("basename", "language", "speaker", "duration_control")} for e in entries],

@@ -28,12 +28,27 @@ def feature_path(save_dir, kind: str, basename: str, speaker: str, language: str
     return Path(save_dir) / kind / SEP.join([basename, speaker, language, suffix])
 
 
-class FeatureDataset(torch.utils.data.Dataset):
-    """Training / teacher-forcing items of ``FastSpeechDataset`` (the inference branch: ``SynthesisDataset``)."""
+ATTN_PRIOR_MODES = ("files", "computed")
 
-    def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, text_processor=None):
+
+def _attn_prior_mode(mode: str) -> str:
+    if mode not in ATTN_PRIOR_MODES:
+        raise ValueError(f"attn_prior must be one of {ATTN_PRIOR_MODES}, got {mode!r}")
+    return mode
+
+
+class FeatureDataset(torch.utils.data.Dataset):
+    """Training / teacher-forcing items of ``FastSpeechDataset`` (the inference branch: ``SynthesisDataset``).
+
+    ``attn_prior`` (a model that learns its alignment): ``"files"`` loads every item's ``attn/...-attn-prior.pt`` as the
+    reference does; ``"computed"`` opens no prior file and leaves the item's ``duration`` None -- the model computes the
+    prior on the GPU from the batch's lengths (``hip.attn_prior``)."""
+
+    def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, text_processor=None,
+                 attn_prior: str = "files"):
         from .config import TextProcessor
 
+        self.attn_prior = _attn_prior_mode(attn_prior)
         self.entries, self.config = entries, config
         self.lang2id, self.speaker2id = lang2id, speaker2id
         self.text_processor = text_processor or TextProcessor(config.text)
@@ -102,7 +117,9 @@ class FeatureDataset(torch.utils.data.Dataset):
         mel = self._load(bn, speaker, language, "spec", f"spec-{self.sampling_rate}-{self.spec_type}.pt").transpose(0, 1)
         chars = m.target_text_representation_level == L.characters
         if m.learn_alignment:
-            duration = self._load(bn, speaker, language, "attn", ("characters" if chars else "phones") + "-attn-prior.pt")
+            duration = None
+            if self.attn_prior == "files":
+                duration = self._load(bn, speaker, language, "attn", ("characters" if chars else "phones") + "-attn-prior.pt")
         else:
             try:
                 duration = self._load(bn, speaker, language, "duration", "duration.pt")
@@ -625,7 +642,8 @@ class SynthesisDataset(torch.utils.data.Dataset):
     :153-154, :192-194, :212-214): the 15 keys of ``FeatureDataset``'s items in the same order, with ``mel`` /
     ``duration`` / ``energy`` / ``pitch`` None in free synthesis, ``is_last_input_chunk`` (default True) and
     ``duration_control`` from the entry.  With ``teacher_forcing_dir`` the mel and the durations (the attention prior of
-    a model that learns its alignment) are loaded from that directory exactly as ``FeatureDataset`` loads them.
+    a model that learns its alignment) are loaded from that directory exactly as ``FeatureDataset`` loads them
+    (``attn_prior="computed"``: no prior file is opened, ``duration`` stays None and the model computes the prior).
 
     Tokens: the entry's ``character_tokens`` / ``phone_tokens`` column through ``encode_escaped_string_sequence`` when
     present, else its raw ``characters`` / ``phones`` text through ``TextProcessor.encode_text``.  There is no G2P, no
@@ -640,12 +658,13 @@ class SynthesisDataset(torch.utils.data.Dataset):
     constructor: ``token_counts`` is what ``synthesis_batches`` takes."""
 
     def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, teacher_forcing_dir=None,
-                 style_reference=None, text_processor=None):
+                 style_reference=None, text_processor=None, attn_prior: str = "files"):
         import sys
 
         from .config import TargetTrainingTextRepresentationLevel as L
         from .config import TextProcessor
 
+        self.attn_prior = _attn_prior_mode(attn_prior)
         self.entries, self.config = entries, config
         self.lang2id, self.speaker2id = lang2id, speaker2id
         self.text_processor = text_processor or TextProcessor(config.text)
@@ -710,8 +729,9 @@ class SynthesisDataset(torch.utils.data.Dataset):
         if self.teacher_forcing:
             mel = self._load(bn, speaker, language, "spec", f"spec-{self.sampling_rate}-{self.spec_type}.pt").transpose(0, 1)
             if m.learn_alignment:
-                duration = self._load(bn, speaker, language, "attn",
-                                      ("characters" if self.chars else "phones") + "-attn-prior.pt")
+                if self.attn_prior == "files":
+                    duration = self._load(bn, speaker, language, "attn",
+                                          ("characters" if self.chars else "phones") + "-attn-prior.pt")
             else:
                 try:
                     duration = self._load(bn, speaker, language, "duration", "duration.pt")

@@ -152,6 +152,7 @@ SIGNATURES = {
     "fs2hip_pack_spec": "ppppiiip",
     "fs2hip_zero_tail_rows": "pqpiip",
     "fs2hip_utterance_losses": "pipppiifpfpip",  # (the first: const Fs2ScoreMember*, a ctypes array)
+    "fs2hip_attn_prior": "pppiiifp",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -2168,6 +2169,25 @@ def attn_softmax(logits, prior, key_lens, own_keys=False):
     fn = lib().fs2hip_attn_softmax_own_keys if own_keys else lib().fs2hip_attn_softmax
     _ok(fn(_p(logits), _p(prior), _p(key_lens), _p(logprob), _p(soft), B, T1, T2, _stream()), "attn_softmax")
     return logprob, soft
+
+
+def attn_prior(mel_lens, src_lens, Tm, Ts, scaling=1.0, out=None):
+    """The aligner's attention prior from the lengths: ``[B, Tm, Ts]`` fp32, utterance ``b``'s ``betabinom(P - 1, scaling *
+    (i + 1), scaling * (M - i)).pmf(k)`` (``synthetic.beta_binomial_prior``; ``M`` / ``P`` = its lengths clamped to the
+    geometry) in the top-left corner and exact zeros on the padding -- what ``collate`` makes of the per-utterance files and
+    ``pad_batch`` of that.  Evaluated in fp64 on the device; every element of ``out`` is written, none is read."""
+    _chk(mel_lens, torch.int32, "mel_lens"); _chk(src_lens, torch.int32, "src_lens")
+    B, Tm, Ts, scaling = mel_lens.numel(), int(Tm), int(Ts), float(scaling)
+    _req(B > 0 and src_lens.numel() == B, f"attn_prior: {mel_lens.numel()} mel lengths, {src_lens.numel()} text lengths")
+    _req(Tm > 0 and Ts > 0, f"attn_prior: empty geometry (Tm {Tm}, Ts {Ts})")
+    _req(scaling > 0.0, f"attn_prior: scaling must be positive, got {scaling}")
+    if out is None:
+        out = torch.empty(B, Tm, Ts, device=mel_lens.device, dtype=torch.float32)
+    else:
+        _chk(out, torch.float32, "out")
+        _req(tuple(out.shape) == (B, Tm, Ts), f"attn_prior: out is {tuple(out.shape)}, expected {(B, Tm, Ts)}")
+    _ok(lib().fs2hip_attn_prior(_p(mel_lens), _p(src_lens), _p(out), B, Tm, Ts, scaling, _stream()), "attn_prior")
+    return out
 
 
 def mas(x, in_lens, out_lens, is_log=False):

@@ -618,7 +618,8 @@ class FastSpeech2(_Base):
             padded[..., :N_PHONOLOGICAL_FEATURES] = pfs
             b["pfs"] = padded
         if b.get("duration") is not None and torch.is_tensor(b["duration"]):
-            # learned alignment: "duration" carries the (B, Tm, Ts) attention prior (fs2/dataset.py:274-281)
+            # learned alignment: "duration" carries the (B, Tm, Ts) attention prior (fs2/dataset.py:274-281) -- or nothing
+            # (None / a list of None), and the aligner computes the prior on the device from the lengths (hip.attn_prior)
             prior = self.config.model.learn_alignment and b["duration"].dim() == 3
             b["duration"] = self._dev(b["duration"], torch.float32 if prior else torch.int32)
         return b
@@ -952,6 +953,8 @@ class FastSpeech2(_Base):
                 geo.append((k, tuple(v.shape)) if v.dim() else (k, int(v)))
             elif isinstance(v, (int, float)) or v is None:
                 geo.append((k, v))
+            elif k == "duration" and isinstance(v, (list, tuple)) and all(x is None for x in v):
+                geo.append((k, None))  # (collate's column of items without a prior: the aligner computes it in the step)
         t = self.config.training
         bin_w = min(self.current_epoch / t.attn_bin_loss_warmup_epochs, 1.0) if self.config.model.learn_alignment else 0.0
         sync = self.grad_sync

@@ -773,6 +773,10 @@ class Aligner:
         q2 = H.linear_fwd(q1, *self._w("q2"), epi=H.EPI_ACT, act="relu")
         qenc = H.linear_fwd(q2, *self._w("q4"))
         logits = H.attn_dist(qenc, kenc)
+        if not torch.is_tensor(prior):
+            # a batch without a prior (None, or collate's list of None): it is a function of the two lengths alone, computed
+            # here at the step's geometry -- a launch like any other, so a recorded plan replays it and feeds no prior
+            prior = H.attn_prior(mel_lens, src_lens, Tm, Ts)
         # (exact lengths: the padded keys' logits are finite -- they must not enter log_softmax's normaliser, or attn_logprob
         # and with it the CTC score follows the batch's longest text)
         logprob, soft = H.attn_softmax(logits, prior, src_lens, own_keys=self.env.exact)

@@ -629,6 +629,18 @@ int fs2hip_utterance_losses(const Fs2ScoreMember* members, int n, const float* s
 int fs2hip_attn_softmax_own_keys(const float* logits, const float* prior, const int* key_lens, float* logprob,
                                  float* soft, int B, int T1, int T2, void* stream);
 
+/* The aligner's attention prior computed from the lengths (the matrix the data pipeline otherwise loads from
+ * attn/<name>-attn-prior.pt, collates and copies to the device): prior [B][Tm][Ts] fp32, dense, EVERY element written and
+ * none read (the caller need not clear it).  Per utterance M = clamp(mel_lens[b], 0, Tm), P = clamp(src_lens[b], 0, Ts),
+ * n = P - 1; for frame i < M and key k < P, with a = scaling * (i + 1) and b' = scaling * (M - i):
+ *     prior[b][i][k] = C(n, k) * Beta(k + a, n - k + b') / Beta(a, b')          (= scipy betabinom(n, a, b').pmf(k))
+ * and exactly 0.f where i >= M or k >= P (what zero padding to the batch's or a bucket's geometry gives); the P = 1 row
+ * is exactly 1.  Evaluated in fp64 in log space -- lgamma(n+1) - lgamma(k+1) - lgamma(n-k+1) + lgamma(k+a) + lgamma(n-k+b')
+ * - lgamma(n+a+b') - (lgamma(a) + lgamma(b') - lgamma(a+b')), one exp -- and rounded to fp32 once, at the store: the terms
+ * reach about 7 000 at 1291 x 200, where one fp32 ulp is 5e-4.  -22: a null pointer, a non-positive extent, scaling <= 0. */
+int fs2hip_attn_prior(const int* mel_lens, const int* src_lens, float* prior, int B, int Tm, int Ts, float scaling,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
