@@ -169,6 +169,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with -T: also write OUTPUT_DIR/scores-<step>.psv, every utterance's own losses (as if it were scored alone: "
                          "implies --exact-lengths) and coverage scores, worst first (the reference's return_scores, batched)")
     sy.add_argument("--scores-only", action="store_true", help="with --return-scores: write the score file and no spectrograms")
+    sy.add_argument("--write-alignments", action="store_true",
+                    help="also write OUTPUT_DIR/synthesized_alignment/*--alignment.pt: every text's tokens, per-token durations in "
+                         "frames, and the pitch and energy predictions (a dict of tensors; fs2hip_pack_rows packs them into the "
+                         "copy that carries the spectrograms).  With -T and a model that learns its alignment the durations are the "
+                         "aligner's, and OUTPUT_DIR/duration/*--duration.pt is written for training a learn_alignment: false model")
     sy.add_argument("--compute-attn-prior", action="store_true",
                     help="with -T, " + "a model that learns its alignment: open no attn/*-attn-prior.pt file and compute the attention prior on the GPU "
                          "from each batch's lengths (fs2hip_attn_prior; this project's beta-binomial definition).  Ignored when "
@@ -699,6 +704,28 @@ def synthesis_file_names(dataset, out_dir, global_step: int) -> list:
     return names
 
 
+def alignment_file_names(dataset, out_dir, global_step: int) -> list:
+    """The files ``AlignmentWriter`` will write for ``dataset``, in input order (one per text: chunks are joined)."""
+    from .data import SEP, slugify, truncate_basename
+    names, text = [], ""
+    for e in dataset.entries:
+        text += e.get("characters", e.get("phones", "text"))  # (``raw_text`` of the item)
+        if e.get("is_last_input_chunk", True):
+            names.append(str(Path(out_dir) / "synthesized_alignment" / SEP.join(
+                [truncate_basename(slugify(text)), e.get("speaker") or "default", e.get("language") or "default",
+                 f"ckpt={global_step}", "alignment.pt"])))
+            text = ""
+    return names
+
+
+def duration_file_names(dataset, out_dir) -> list:
+    """The ``duration/`` files ``AlignmentWriter`` writes for a teacher-forced dataset of a model that learns its alignment:
+    one per entry, under the filelist's basename."""
+    from .data import feature_path
+    return [str(feature_path(out_dir, "duration", e["basename"], e.get("speaker") or "default",
+                             e.get("language") or "default", "duration.pt")) for e in dataset.entries]
+
+
 def synthesize_command(args) -> int:
     """``fs2l synthesize`` (reference ``fs2/cli/synthesize.py:466-700``): checkpoint + text -> ``.pt`` spectrograms in
     ``OUTPUT_DIR/synthesized_spec/``, one GPU.  Argument errors come before anything expensive is loaded."""
@@ -716,8 +743,8 @@ def synthesize_command(args) -> int:
                          "durations, which free synthesis does not have")
     if args.scores_only and not args.return_scores:
         raise SystemExit("--scores-only goes with --return-scores")
-    from .data import (PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores, synthesis_batches,
-                       synthesis_entries)
+    from .data import (AlignmentWriter, PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores,
+                       synthesis_batches, synthesis_entries)
     print(f"Loading checkpoint from {args.model_path}", file=sys.stderr)
     if args.dry_run:
         ckpt = torch.load(args.model_path, map_location="cpu", weights_only=False)
@@ -754,6 +781,10 @@ def synthesize_command(args) -> int:
             plan["scores_file"] = str(scores.path)
             for e, cov in zip(plan["entries"], coverage_scores(dataset.tokens)):
                 e.update(cov)
+        if args.write_alignments:
+            plan["alignment_files"] = alignment_file_names(dataset, args.output_dir, global_step)
+            if dataset.teacher_forcing and config.model.learn_alignment:
+                plan["duration_files"] = duration_file_names(dataset, args.output_dir)
         print(json.dumps(plan))
         return 0
     from .config import InferenceControl
@@ -763,16 +794,21 @@ def synthesize_command(args) -> int:
     if not args.scores_only:
         writer = PackedSpecWriter(args.output_dir, model.output_key, global_step, audio.input_sampling_rate,
                                   getattr(audio, "spec_type", "mel-librosa"), n_mels=audio.n_mels)
+    alignments = None
+    if args.write_alignments:
+        alignments = AlignmentWriter(args.output_dir, global_step, dataset.text_processor.symbols)
     control = InferenceControl(pitch=args.pitch_control, energy=args.energy_control, duration=args.duration_control)
     t0 = time.perf_counter()
     res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort, exact_lengths=args.exact_lengths,
-                     scores=scores)
+                     scores=scores, alignments=alignments)
     torch.cuda.synchronize()
     report = {"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
               "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),
               "output_dir": str(writer.dir if writer is not None else args.output_dir)}
     if scores is not None:
         report["scores_file"] = str(scores.close())
+    if alignments is not None:
+        report["alignment_files"] = len(res["alignment_files"])
     print(json.dumps(report), flush=True)
     return 0
 

@@ -179,6 +179,15 @@ class TextProcessor:
                 i += 1  # unknown symbol: dropped
         return out
 
+    def decode_tokens(self, ids) -> list[str]:
+        """The symbols of a sequence of token ids (a list or a 1-D tensor), one string per id: the inverse of the two
+        encoders (the reference's ``TextProcessor.decode_tokens(..., join_character=None)``).  An id outside the table is
+        an error."""
+        ids = [int(i) for i in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+        bad = [i for i in ids if not 0 <= i < len(self.symbols)]
+        if bad:
+            raise ValueError(f"decode_tokens: ids {bad[:5]} are outside the symbol table (0 .. {len(self.symbols) - 1})")
+        return [self.symbols[i] for i in ids]
 
     def encode_escaped_string_sequence(self, tokens) -> list[int]:
         """Token sequence as stored by the preprocessor: symbols separated by '/' ('\\/' is a literal slash);

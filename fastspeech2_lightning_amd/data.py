@@ -468,6 +468,155 @@ class PackedSpecWriter(SpecWriter):
         return len(self._held) + len(self._chunks)
 
 
+class AlignmentWriter:
+    """Per-token durations, pitch and energy beside the spectrograms ``PackedSpecWriter`` writes: which frames belong to
+    which token -- what the reference's TextGrid / ReadAlong writers are built on (fs2/prediction_writing_callback.py:
+    331-392) -- as data, one ``.pt`` file per text:
+
+        ``OUT/synthesized_alignment/<basename>--<speaker>--<language>--ckpt=<step>--alignment.pt``
+
+    with ``PackedSpecWriter``'s basename rule (``truncate_basename(slugify(text))``), input-order release and chunk
+    concatenation.  The file is a dict of tensors, strings, ints and lists of strings (``torch.load(...,
+    weights_only=True)`` reads it): ``text`` int32 [n] token ids, ``symbols`` their n strings, ``duration`` int32 [n] in
+    frames, ``frames`` = ``duration.sum()`` = the frame count of the spectrogram file, ``pitch`` / ``energy`` fp32 ([n]
+    for a ``"phone"``-level predictor, [frames] for a ``"frame"``-level one: ``pitch_level`` / ``energy_level``),
+    ``duration_source`` -- ``"predicted"`` (free synthesis), ``"given"`` (teacher forcing on stored durations) or
+    ``"aligner"`` (teacher forcing through a learned aligner: its MAS durations) -- and ``raw_text``.  No time in
+    seconds: frames times the hop size over the sampling rate is the reader's business.
+
+    ``duration`` describes the spectrogram actually written: where the model's ``max_length`` cut the output (fewer
+    frames than the durations add up to), the cumulative ends are clipped to the frame count, ``d'[j] = min(cum_j, frames)
+    - min(cum_{j-1}, frames)``, so trailing tokens shrink to what is left of them (possibly 0).
+
+    ``symbols``: the model's symbol table (``TextProcessor(config.text).symbols``) or the ``TextProcessor`` itself.
+
+    ``write_packed`` takes a batch's packed HOST buffer (fp32; int32 members are read through a view), the members'
+    places in it, the batch, the items' positions in the input and every utterance's frame count; each piece is cloned
+    out of the buffer (the caller reuses it).  With ``duration_files=True`` every utterance's durations also go to
+    ``OUT/duration/<basename>--<speaker>--<language>--duration.pt`` under the FILELIST's basename (``batch["basename"]``), a
+    1-D int64 tensor: the layout ``FeatureDataset`` loads for a ``learn_alignment: false`` model, so that a corpus aligned
+    by a trained ``learn_alignment`` model can train a fixed-duration one."""
+
+    LEVELS = ("phone", "frame")
+    SOURCES = ("predicted", "given", "aligner")
+
+    def __init__(self, out_dir, global_step: int = 0, symbols=None):
+        self.out_dir = Path(out_dir)
+        self.dir = self.out_dir / "synthesized_alignment"
+        self.duration_dir = self.out_dir / "duration"
+        self.dir.mkdir(parents=True, exist_ok=True)
+        self.global_step = int(global_step)
+        table = getattr(symbols, "symbols", symbols)
+        if table is None:
+            raise ValueError("AlignmentWriter: the model's symbol table is required (TextProcessor(config.text).symbols)")
+        self.symbols = list(table)
+        self.duration_files = []
+        self._held, self._next, self._chunks = {}, 0, []
+
+    def filename(self, basename, speaker, language) -> Path:
+        return self.dir / SEP.join([basename, speaker, language, f"ckpt={self.global_step}", "alignment.pt"])
+
+    def duration_filename(self, basename, speaker, language) -> Path:
+        return feature_path(self.out_dir, "duration", basename, speaker, language, "duration.pt")
+
+    @staticmethod
+    def clip(duration: torch.Tensor, frames: int) -> torch.Tensor:
+        """``duration`` [n] with its cumulative ends clipped to ``frames`` (see the class): sums to ``frames``."""
+        cum = duration.to(torch.int64).cumsum(0).clamp(max=int(frames))
+        return torch.diff(cum, prepend=cum.new_zeros(1)).to(torch.int32)
+
+    def write_packed(self, packed: torch.Tensor, members: dict, batch: dict, positions, frames,
+                     duration_source: str = "predicted", duration_files: bool = False) -> list[Path]:
+        """``members``: ``{"duration" | "pitch" | "energy": (start, offsets, level)}`` -- the member's first element in
+        ``packed``, its B + 1 element offsets from there (``hip.pack_rows``'s), and ``"phone"`` / ``"frame"``.
+        ``frames``: every utterance's frame count in the written spectrogram (``tgt_lens``)."""
+        if duration_source not in self.SOURCES:
+            raise ValueError(f"AlignmentWriter: duration_source must be one of {self.SOURCES}, got {duration_source!r}")
+        if sorted(members) != ["duration", "energy", "pitch"]:
+            raise ValueError(f"AlignmentWriter: members must be duration, pitch and energy, got {sorted(members)}")
+        B = len(positions)
+        frames = [int(f) for f in frames]
+        if len(frames) != B:
+            raise ValueError(f"AlignmentWriter: {len(frames)} frame counts for {B} utterances")
+        table = {}
+        for name, (start, offsets, level) in members.items():
+            offsets = [int(o) for o in offsets]
+            if level not in self.LEVELS or (name == "duration" and level != "phone"):
+                raise ValueError(f"AlignmentWriter: {name} cannot be at level {level!r}")
+            if len(offsets) != B + 1:
+                raise ValueError(f"AlignmentWriter: {len(offsets)} {name} offsets for {B} utterances")
+            if offsets[0] != 0 or any(b < a for a, b in zip(offsets, offsets[1:])) or start < 0 \
+                    or start + offsets[-1] > packed.numel():
+                raise ValueError(f"AlignmentWriter: the {name} offsets {offsets} from element {start} do not delimit rows "
+                                 f"of a buffer of {packed.numel()} elements")
+            table[name] = (int(start), offsets, level)
+        last = batch.get("is_last_input_chunk") or [True] * B
+        ints = packed.view(torch.int32)
+        written_durations = []
+        for i, pos in enumerate(positions):
+            pos = int(pos)
+            if pos in self._held or pos < self._next:
+                raise ValueError(f"AlignmentWriter: position {pos} delivered twice")
+            start, off, _ = table["duration"]
+            dur = ints[start + off[i]:start + off[i + 1]].clone()
+            n = dur.numel()
+            total = int(dur.sum())
+            if frames[i] > total or frames[i] < 0:
+                raise ValueError(f"AlignmentWriter: utterance {pos} has {frames[i]} frames but durations that add up to {total}")
+            piece = {"duration": self.clip(dur, frames[i]) if total != frames[i] else dur, "frames": frames[i]}
+            for name in ("pitch", "energy"):
+                start, off, level = table[name]
+                want = n if level == "phone" else frames[i]
+                if off[i + 1] - off[i] != want:
+                    raise ValueError(f"AlignmentWriter: utterance {pos}: {off[i + 1] - off[i]} {name} values at the {level} "
+                                     f"level, where it has {n} tokens and {frames[i]} frames")
+                piece[name] = packed[start + off[i]:start + off[i + 1]].clone()
+                piece[name + "_level"] = level
+            text = torch.as_tensor(batch["text"][i]).reshape(-1)
+            if text.numel() < n:
+                raise ValueError(f"AlignmentWriter: utterance {pos} has {n} durations for {text.numel()} tokens")
+            piece["text"] = text[:n].to(torch.int32).clone()
+            piece["raw_text"], piece["duration_source"] = batch["raw_text"][i], duration_source
+            speaker, language = batch["speaker"][i], batch["language"][i]
+            if duration_files:
+                path = self.duration_filename(batch["basename"][i], speaker, language)
+                path.parent.mkdir(parents=True, exist_ok=True)
+                torch.save(piece["duration"].to(torch.int64), path)
+                written_durations.append(path)
+            self._held[pos] = (piece, speaker, language, last[i] is None or bool(last[i]))
+        self.duration_files.extend(written_durations)
+        written = []
+        while self._next in self._held:
+            piece, speaker, language, is_last = self._held.pop(self._next)
+            self._next += 1
+            self._chunks.append(piece)
+            if is_last:
+                written.append(self._save(self._chunks, speaker, language))
+                self._chunks = []
+        return written
+
+    def _save(self, chunks, speaker, language) -> Path:
+        first = chunks[0]
+        for c in chunks[1:]:
+            for k in ("pitch_level", "energy_level", "duration_source"):
+                if c[k] != first[k]:
+                    raise ValueError(f"AlignmentWriter: the chunks of one text disagree on {k}: {first[k]!r}, {c[k]!r}")
+        cat = lambda k: torch.cat([c[k] for c in chunks]) if len(chunks) > 1 else first[k]  # noqa: E731
+        raw_text = "".join(c["raw_text"] for c in chunks)
+        text = cat("text")
+        symbols = [self.symbols[i] for i in text.tolist()]
+        record = {"text": text, "symbols": symbols, "duration": cat("duration"), "frames": sum(c["frames"] for c in chunks),
+                  "pitch": cat("pitch"), "energy": cat("energy"), "pitch_level": first["pitch_level"],
+                  "energy_level": first["energy_level"], "duration_source": first["duration_source"], "raw_text": raw_text}
+        path = self.filename(truncate_basename(slugify(raw_text)), speaker, language)
+        torch.save(record, path)
+        return path
+
+    def pending(self) -> int:
+        """Pieces held back: positions not yet reached, plus chunks of a text whose last chunk has not arrived."""
+        return len(self._held) + len(self._chunks)
+
+
 def coverage_scores(token_lists) -> list[dict]:
     """The two coverage scores the reference attaches to every row when it scores a corpus (fs2/cli/synthesize.py:389-409,
     there with nltk's ``ngrams``): ``[{"phone_coverage_score": x, "trigram_coverage_score": y}]``, one per entry.

@@ -153,6 +153,7 @@ SIGNATURES = {
     "fs2hip_zero_tail_rows": "pqpiip",
     "fs2hip_utterance_losses": "pipppiifpfpip",  # (the first: const Fs2ScoreMember*, a ctypes array)
     "fs2hip_attn_prior": "pppiiifp",
+    "fs2hip_pack_rows": None,  # (const Fs2PackMember*, int, int, void*): set below
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -182,6 +183,7 @@ def lib():
         L.fs2hip_reduce_slabs_multi.argtypes = [C.POINTER(SlabJob), C.c_int, C.c_void_p]
         L.fs2hip_transpose_cast_bf16_multi.argtypes = [C.POINTER(TransposeJob), C.c_int, C.c_void_p]
         L.fs2hip_pad_batch.argtypes = [C.POINTER(PadMember), C.c_int, C.c_void_p]
+        L.fs2hip_pack_rows.argtypes = [C.POINTER(PackMember), C.c_int, C.c_int, C.c_void_p]
         L.fs2hip_plan_op_id.argtypes = [C.c_char_p]
         L.fs2hip_plan_events_create.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         L.fs2hip_plan_events_destroy.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -1954,6 +1956,51 @@ def pack_spec(y, lens, packed=None, offsets=None):
     _req(offsets.numel() >= B + 1, f"pack_spec: offsets holds {offsets.numel()} entries, {B + 1} are written")
     _ok(lib().fs2hip_pack_spec(_p(y), _p(lens), _p(packed), _p(offsets), B, Tm, C_, _stream()), "pack_spec")
     return packed, offsets
+
+
+PACK_MAX_MEMBERS = 8   # FS2_PACK_MAX_MEMBERS
+
+
+class PackMember(C.Structure):  # mirrors Fs2PackMember (include/fs2hip.h)
+    _fields_ = [("src", C.c_void_p), ("lens", C.c_void_p), ("dst", C.c_void_p), ("offsets", C.c_void_p), ("T", C.c_int),
+                ("pad_", C.c_int)]
+
+
+def pack_rows(members, B):
+    """Ragged pack of up to ``PACK_MAX_MEMBERS`` small ``[B, T]`` tensors in one call (``fs2hip_pack_rows``: two launches,
+    nothing is read back).  ``members``: ``[(src, lens, dst, offsets)]`` -- ``src`` [B, T] int32 or fp32, ``lens`` [B] int32
+    in GPU memory (clamped to 0..T on the device), ``dst`` a 1-D tensor of ``src``'s dtype (or fp32: the copy is
+    byte-wise, a slice of a float buffer takes int32 rows) that holds the worst case ``B * T`` -- only
+    ``dst[:offsets[B]]`` is written -- and ``offsets`` [B + 1] int64, written here: element offsets of the utterances'
+    rows in ``dst``, the total last.  ``dst`` / ``offsets`` None: allocated.  Returns ``[(dst, offsets)]``."""
+    members = list(members)
+    _req(isinstance(B, int) and B > 0, f"pack_rows: B = {B!r} (at least 1)")
+    _req(0 < len(members) <= PACK_MAX_MEMBERS, f"pack_rows: 1 to {PACK_MAX_MEMBERS} members per call, got {len(members)}")
+    table = (PackMember * len(members))()
+    res = []
+    for i, (m, (src, lens, dst, offsets)) in enumerate(zip(table, members)):
+        _req(isinstance(src, torch.Tensor) and src.dtype in (torch.float32, torch.int32),
+             f"pack_rows: member {i}: src must be an fp32 or int32 tensor")
+        _chk(src, src.dtype, f"member {i} src")
+        _chk(lens, torch.int32, f"member {i} lens")
+        _req(src.dim() == 2 and src.shape[0] == B and src.shape[1] > 0,
+             f"pack_rows: member {i}: src {tuple(src.shape)} is not [B = {B}, T >= 1]")
+        _req(lens.numel() == B, f"pack_rows: member {i}: lens has {lens.numel()} entries for {B} utterances")
+        T = src.shape[1]
+        if dst is None:
+            dst = torch.empty(B * T, device=src.device, dtype=src.dtype)
+        if offsets is None:
+            offsets = torch.empty(B + 1, device=src.device, dtype=torch.int64)
+        _req(isinstance(dst, torch.Tensor) and dst.dtype in (src.dtype, torch.float32),
+             f"pack_rows: member {i}: dst must be {src.dtype} (or fp32: the copy is byte-wise)")
+        _chk(dst, dst.dtype, f"member {i} dst")
+        _chk(offsets, torch.int64, f"member {i} offsets")
+        _req(dst.numel() >= B * T, f"pack_rows: member {i}: dst holds {dst.numel()} elements, the worst case is {B * T}")
+        _req(offsets.numel() >= B + 1, f"pack_rows: member {i}: offsets holds {offsets.numel()} entries, {B + 1} are written")
+        m.src, m.lens, m.dst, m.offsets, m.T = _p(src), _p(lens), _p(dst), _p(offsets), T
+        res.append((dst, offsets))
+    _ok(lib().fs2hip_pack_rows(table, len(members), B, _stream()), "pack_rows")
+    return res
 
 
 #: launches of ``zero_tail_rows`` so far (a measurement aid: the masks one exact-length forward adds)

@@ -765,7 +765,7 @@ class FastSpeech2(_Base):
         self.env.join()  # variance predictors of a teacher-forced forward ran on the side stream under the decoder
         if not self._in_step:  # called directly (evaluation, teacher forcing): raise at once, as the reference does
             self.check_bad_data()
-        return {
+        out = {
             "output": output, "postnet_output": postnet_output,
             "src_mask": H.mask_from_lens(src_lens, Ts), "src_lens": src_lens,
             "tgt_mask": H.mask_from_lens(tgt_lens, Tm), "tgt_lens": tgt_lens,
@@ -775,6 +775,11 @@ class FastSpeech2(_Base):
             "pitch_prediction": va["pitch_prediction"], "pitch_target": va["pitch_target"],
             "text_input": text,
         }
+        if inference:
+            # the durations the length regulator ran on, [B, Ts] int32 (fs2/variance_adaptor.py:358-366, :410): predicted and
+            # rounded in free inference, the batch's under teacher forcing, the aligner's (MAS) when it learns its alignment
+            out["duration_rounded"] = va["duration_rounded"]
+        return out
 
     __call__ = forward
 

@@ -25,6 +25,14 @@ row count, so two batchings agree to fp32 summation order, not bit for bit.
 the offsets, so it leaves the GPU inside the copy that carries the spectrograms -- same copy stream, same single wait.
 ``exact_lengths`` is forced on: a score must not follow ``-b`` or the sort order.  Without a spectrogram writer (scores
 only) nothing is packed and the copy is the header alone.
+
+``alignments`` (a ``data.AlignmentWriter``; ``fs2l synthesize --write-alignments``) adds what says which frames belong to
+which token: ``duration_rounded`` and the pitch and energy predictions, cut to every utterance's own lengths on the device
+by ONE ``hip.pack_rows`` call (two small launches) into an alignment block between the header and the spectrograms --
+token-level members by ``src_lens``, frame-level ones by ``tgt_lens``, their offset tables in the header.  The block's size
+comes from lengths the host already has (the collated ``src_lens``, the frame totals above), so the batch still leaves in
+the one copy and is waited for once; the device's offsets are checked against the host's, as the spectrograms' are.
+Without ``alignments`` not one launch, allocation or header byte changes.
 """
 from __future__ import annotations
 
@@ -38,16 +46,22 @@ from .model import LOSS_KEYS
 
 
 class _Slot:
-    """One device buffer + its pinned host twin, both float32: [header | payload].  The header holds the batch's B + 1
-    int64 offsets (2 floats each, rounded up to 4 floats so that what follows starts 16-byte aligned) and, when the batch
-    is scored, its [B, 8] table of per-utterance losses."""
+    """One device buffer + its pinned host twin, both float32: [header | alignment block | payload].  The header holds the
+    batch's B + 1 int64 offsets (2 floats each, rounded up to 4 floats so that what follows starts 16-byte aligned), then
+    -- when alignments are written -- one such table per member of the alignment block, and, when the batch is scored,
+    its [B, 8] table of per-utterance losses last.  The alignment block (only with alignments) holds the members' packed
+    rows back to back and is rounded up to 4 floats, so the payload starts 16-byte aligned with or without it."""
 
     def __init__(self, device):
         self.device, self.dev, self.host = device, None, None
 
     @staticmethod
-    def header(B: int, scored: bool = False) -> int:
-        return -(-2 * (B + 1) // 4) * 4 + (_COLS * B if scored else 0)
+    def table(B: int) -> int:
+        return -(-2 * (B + 1) // 4) * 4
+
+    @staticmethod
+    def header(B: int, scored: bool = False, members: int = 0) -> int:
+        return (1 + members) * _Slot.table(B) + (_COLS * B if scored else 0)
 
     def reserve(self, floats: int):
         if self.dev is None or self.dev.numel() < floats:
@@ -60,17 +74,21 @@ _COLS = len(LOSS_KEYS) + 1   # columns of the score table: the loss terms and th
 
 
 def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2,
-               exact_lengths: bool = False, scores=None) -> dict:
+               exact_lengths: bool = False, scores=None, alignments=None) -> dict:
     """Synthesizes every item of ``dataset`` (``data.SynthesisDataset``) and writes the spectrograms through ``writer``
     (``data.PackedSpecWriter``), in input order.  Returns ``{"files": [paths], "utterances": n, "frames": n, "batches": n}``.
     Per batch the host reads the GPU once inside the forward pass (the frame totals; nothing for a teacher-forced batch)
     and waits once, for the copy event.  ``exact_lengths``: see the module's docstring.  ``scores`` (``data.ScoreWriter``):
     every entry's per-utterance losses and coverage scores are added to it (the caller closes it); the dataset must be
-    teacher-forced, ``exact_lengths`` is forced on, and ``writer`` may be None (scores only)."""
+    teacher-forced, ``exact_lengths`` is forced on, and ``writer`` may be None (scores only).  ``alignments``
+    (``data.AlignmentWriter``): every text's durations, pitch and energy are written through it (the result gains
+    ``"alignment_files"``, and ``"duration_files"`` for a teacher-forced dataset of a model that learns its alignment);
+    ``writer`` may be None here too.  At least one of the three is required."""
     if depth < 1:
         raise ValueError("synthesize: depth >= 1")
-    if writer is None and scores is None:
-        raise ValueError("synthesize: a PackedSpecWriter is required")
+    if writer is None and scores is None and alignments is None:
+        raise ValueError("synthesize: a PackedSpecWriter is required (or a ScoreWriter as scores=, or an AlignmentWriter as "
+                         "alignments=): there is nothing to write")
     scored = scores is not None
     if scored:
         if not getattr(dataset, "teacher_forcing", False):
@@ -84,13 +102,39 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
     batches = synthesis_batches(dataset.token_counts, batch_size, sort)
     was_training = model.training
     model.eval()
-    files, frames = [], 0
-    pending = []   # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys)], oldest first
+    files, frames, alignment_files = [], 0, []
+    aligned = alignments is not None
+    if aligned:
+        vp = model.config.model.variance_predictors
+        levels = {"duration": "phone", "pitch": vp.pitch.level.value, "energy": vp.energy.level.value}
+        teacher_forced = bool(getattr(dataset, "teacher_forcing", False))
+        duration_source = ("aligner" if learn_alignment else "given") if teacher_forced else "predicted"
+    # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys, alignment block)], oldest first
+    pending = []
 
     def finish(job):
         nonlocal frames
-        slot, event, hdr, total, expect, cpu_batch, positions, keys = job
+        slot, event, hdr, total, expect, cpu_batch, positions, keys, block = job
         event.synchronize()   # the one wait of this batch
+        base = hdr
+        if writer is not None:
+            offsets = slot.host[:2 * len(expect)].view(torch.int64)
+            if offsets.tolist() != expect:
+                raise RuntimeError("synthesize: the frame counts on the GPU differ from the host's (durations that do not add "
+                                   f"up to the mel lengths?): offsets {offsets.tolist()} against {expect}")
+        if aligned:
+            ablock, members = block
+            tab = _Slot.table(len(positions))
+            for k, (name, (start, want, level)) in enumerate(members.items()):
+                got = slot.host[(1 + k) * tab:(1 + k) * tab + 2 * len(want)].view(torch.int64).tolist()
+                if got != want:
+                    raise RuntimeError(f"synthesize: the {name} lengths on the GPU differ from the host's ({level} level: "
+                                       f"{'token' if level == 'phone' else 'frame'} counts that do not match the batch's?): "
+                                       f"offsets {got} against {want}")
+            alignment_files.extend(alignments.write_packed(
+                slot.host[hdr:hdr + ablock], members, cpu_batch, positions, [n // n_mels for n in _diff(expect)],
+                duration_source=duration_source, duration_files=teacher_forced and learn_alignment))
+            base += ablock   # (the payload lies behind the alignment block)
         if scored:
             B = len(positions)
             table = slot.host[hdr - _COLS * B:hdr].view(B, _COLS).tolist()
@@ -100,13 +144,8 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 rec.update((k, row[LOSS_KEYS.index(k)]) for k in keys)
                 scores.add(pos, rec)
         frames += expect[-1] // n_mels
-        if writer is None:
-            return
-        offsets = slot.host[:2 * len(expect)].view(torch.int64)
-        if offsets.tolist() != expect:
-            raise RuntimeError("synthesize: the frame counts on the GPU differ from the host's (durations that do not add "
-                               f"up to the mel lengths?): offsets {offsets.tolist()} against {expect}")
-        files.extend(writer.write_packed(slot.host[hdr:hdr + total], offsets, cpu_batch, positions))
+        if writer is not None:
+            files.extend(writer.write_packed(slot.host[base:base + total], offsets, cpu_batch, positions))
 
     try:
         with torch.cuda.device(device):
@@ -125,24 +164,49 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 expect = [0]
                 for n in lens_host.tolist():
                     expect.append(expect[-1] + int(n) * C)
-                hdr = _Slot.header(B, scored)
+                hdr = _Slot.header(B, scored, len(levels) if aligned else 0)
                 total = expect[-1] if writer is not None else 0   # (scores only: the header is all that travels)
                 slot = slots[i % depth]   # (its previous batch, i - depth, has been finished: see the drain below)
-                slot.reserve(hdr + (B * Tm * C if writer is not None else 0))
+                ablock, worst, block = 0, 0, None
+                if aligned:
+                    # the alignment block's layout, from lengths the host already has: token counts from the collated
+                    # batch, frame counts from ``lens_host``.  On the device every member may write up to B * T elements
+                    # from its start (lengths that differ from the host's: caught in ``finish``), so that much is reserved
+                    rows = {"duration": out["duration_rounded"], "pitch": out["pitch_prediction"],
+                            "energy": out["energy_prediction"]}
+                    counts = {"phone": cpu_batch["src_lens"].tolist(), "frame": lens_host.tolist()}
+                    members = {}
+                    for name, level in levels.items():
+                        want = [0]
+                        for n in counts[level]:
+                            want.append(want[-1] + int(n))
+                        members[name] = (ablock, want, level)
+                        worst = max(worst, ablock + rows[name].numel())
+                        ablock += want[-1]
+                    ablock, worst = -(-ablock // 4) * 4, -(-worst // 4) * 4
+                    block = (ablock, members)
+                base = hdr + ablock
+                slot.reserve(hdr + worst + (B * Tm * C if writer is not None else 0))
                 keys = None
                 if scored:
                     _, keys = model.utterance_losses(out, cpu_batch, out=slot.dev[hdr - _COLS * B:hdr].view(B, _COLS))
+                if aligned:
+                    tab = _Slot.table(B)
+                    H.pack_rows([(rows[name], out["src_lens" if level == "phone" else "tgt_lens"],
+                                  slot.dev[hdr + start:hdr + start + rows[name].numel()],
+                                  slot.dev[(1 + k) * tab:(1 + k) * tab + 2 * (B + 1)].view(torch.int64))
+                                 for k, (name, (start, _, level)) in enumerate(members.items())], B)
                 if writer is not None:
-                    H.pack_spec(y, out["tgt_lens"], slot.dev[hdr:hdr + B * Tm * C], slot.dev[:2 * (B + 1)].view(torch.int64))
+                    H.pack_spec(y, out["tgt_lens"], slot.dev[base:base + B * Tm * C], slot.dev[:2 * (B + 1)].view(torch.int64))
                 packed_ev = torch.cuda.Event()
                 packed_ev.record(main)
                 copy_stream.wait_event(packed_ev)
                 with torch.cuda.stream(copy_stream):
-                    slot.host[:hdr + total].copy_(slot.dev[:hdr + total], non_blocking=True)
+                    slot.host[:base + total].copy_(slot.dev[:base + total], non_blocking=True)
                     copied_ev = torch.cuda.Event()
                     copied_ev.record(copy_stream)
                 slot.dev.record_stream(copy_stream)
-                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys))
+                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys, block))
                 # the next batch's forward is enqueued before this batch's copy is waited for: only what exceeds
                 # depth - 1 batches in flight is finished now
                 while len(pending) > depth - 1:
@@ -153,7 +217,19 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
         model.train(was_training)
     if writer is not None and writer.pending():
         raise RuntimeError(f"synthesize: {writer.pending()} piece(s) were never written (a text without a last chunk?)")
-    return {"files": files, "utterances": len(dataset), "frames": frames, "batches": len(batches)}
+    res = {"files": files, "utterances": len(dataset), "frames": frames, "batches": len(batches)}
+    if aligned:
+        if alignments.pending():
+            raise RuntimeError(f"synthesize: {alignments.pending()} alignment piece(s) were never written (a text without a "
+                               "last chunk?)")
+        res["alignment_files"] = alignment_files
+        if teacher_forced and learn_alignment:
+            res["duration_files"] = list(alignments.duration_files)
+    return res
+
+
+def _diff(cumulative: list) -> list:
+    return [b - a for a, b in zip(cumulative, cumulative[1:])]
 
 
 def _copy_control(control) -> Optional[object]:

@@ -641,6 +641,32 @@ int fs2hip_attn_softmax_own_keys(const float* logits, const float* prior, const 
 int fs2hip_attn_prior(const int* mel_lens, const int* src_lens, float* prior, int B, int Tm, int Ts, float scaling,
                       void* stream);
 
+/* The way out of the GPU for a synthesized batch's per-token and per-frame quantities -- the rounded durations and the
+ * pitch and energy predictions the reference leaves in its padded output dict (fs2/variance_adaptor.py:399-411) and its
+ * TextGrid writer reads one utterance at a time (fs2/prediction_writing_callback.py:331-347): up to FS2_PACK_MAX_MEMBERS
+ * dense [B][T] tensors of 4-byte elements, each cut to every utterance's own length and packed back to back, in ONE call.
+ * For member m and utterance b, with len = clamp(lens[b], 0, T):
+ *     dst[offsets[b] .. offsets[b] + len) = src[b * T .. b * T + len)
+ * offsets [B + 1] is produced here from lens (one prologue launch, a workgroup per member): offsets[b] = len_0 + ... +
+ * len_{b-1} in elements, offsets[B] = the member's total.  Members may differ in T and in lens (token-level members take
+ * src_lens, frame-level members tgt_lens).  Copied byte-wise: int32 and fp32 alike.  Elements of src at and beyond len
+ * are never read; nothing at or beyond dst[offsets[B]] and nothing but offsets[0 .. B] is written whatever lens holds, so
+ * dst must hold the member's total (B * T elements is the worst case).  dst needs 4-byte alignment only.  The member
+ * table is passed by value in the kernel argument (nothing is uploaded; a launch plan keeps a host copy, as of
+ * Fs2PadMember).  Two launches, no host read, no atomics, no workspace.
+ * FS2HIP_EINVAL, before any launch: members NULL, n < 1 or n > FS2_PACK_MAX_MEMBERS, B <= 0, a member with a null field
+ * or T <= 0. */
+#define FS2_PACK_MAX_MEMBERS 8
+typedef struct {
+  const void* src;    /* [B][T], 4-byte elements (int32 or fp32: copied byte-wise) */
+  const int* lens;    /* [B] in GPU memory; clamped to 0..T on the device */
+  void* dst;          /* packed rows of this member, back to back */
+  long long* offsets; /* [B + 1] element offsets into dst, total last; written by the call */
+  int T;
+  int pad_;
+} Fs2PackMember;
+int fs2hip_pack_rows(const Fs2PackMember* members, int n, int B, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
