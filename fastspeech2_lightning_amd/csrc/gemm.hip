@@ -12,7 +12,7 @@
 
 #include <string.h>
 
-#include "gemm_common.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -188,16 +188,26 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmP p) {
 
 extern "C" int fs2hip_version(void) { return 2; }  // 2: one attention forward / backward entry point per family
 
+int fs2_cu_count() {
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    n_cu = prop.multiProcessorCount;
+  }
+  return n_cu;
+}
+
 namespace {
-// which launcher takes a prepared GemmP: the bf16-storage core, the direct-to-LDS fp32 cores (tile >= 4), the
-// register-staged core (tiles 1-3)
-enum { ROUTE_B = 1, ROUTE_V2 = 2, ROUTE_V1 = 3 };
+// gemm_prepare's decision: the tile's row of gemm_tiles.h (its family names the launcher), the reduction / tap slices
 struct GemmRoute {
-  int core, tile, nz;
+  const Fs2Tile* row;
+  int nz;
 };
 
-// fs2hip_gemm's argument checks and derived fields (p.a normalised, Rper, staged, drop, r_chunk of the BK=16 core) and
-// the choice of core and tile; nothing is enqueued
+// fs2hip_gemm's argument checks and derived fields (p.a normalised, Rper, staged, drop) and the choice of tile; nothing is
+// enqueued
 int gemm_prepare(const Fs2GemmArgs* args, GemmP& p, GemmRoute& route) {
   p.staged = 0;
 #ifdef FS2_PROBES  // phase-ablation builds only (FS2_BUILD_PROBES=1 python -m fastspeech2_lightning_amd.build --force;
@@ -255,9 +265,10 @@ int gemm_prepare(const Fs2GemmArgs* args, GemmP& p, GemmRoute& route) {
     p.drop = fs2_make_drop(a.drop_p, a.drop_seed, a.drop_step);
     const int nzb = (a.shift_operand == 1 ? a.taps : 1) * a.splitk;
     int tb = a.tile;
-    if (tb == 0) tb = (long long)((a.Mc + 127) / 128) * ((a.Nc + 127) / 128) * nzb >= 256 ? 20 : 23;
-    if (tb >= 30 && nzb != 1) return FS2HIP_EINVAL;
-    route = {ROUTE_B, tb, nzb};
+    if (tb == 0) tb = (long long)((a.Mc + 127) / 128) * ((a.Nc + 127) / 128) * nzb >= 256 ? FS2_TILE_B_MANY : FS2_TILE_B_FEW;
+    const Fs2Tile* row = fs2_tile(tb);
+    if (!row || !fs2_family_stored(row->family)) return FS2HIP_EINVAL;
+    route = {row, nzb};
     return 0;
   }
   // vector-load preconditions: the contiguous dimension of every operand is a multiple of 4
@@ -306,8 +317,6 @@ int gemm_prepare(const Fs2GemmArgs* args, GemmP& p, GemmRoute& route) {
       return FS2HIP_EINVAL;
   }
   p.drop = fs2_make_drop(a.drop_p, a.drop_seed, a.drop_step);
-  int chunk = (a.R + a.splitk - 1) / a.splitk;
-  p.r_chunk = ((chunk + BK - 1) / BK) * BK;
   const int nz = (a.shift_operand == 1 ? a.taps : 1) * a.splitk;
   static const int env_tile = getenv("FS2_GEMM_TILE") ? atoi(getenv("FS2_GEMM_TILE")) : 0;  // tuning aid
   int tile = a.tile ? a.tile : env_tile;
@@ -319,49 +328,31 @@ int gemm_prepare(const Fs2GemmArgs* args, GemmP& p, GemmRoute& route) {
     // heuristic (the host autotuner normally picks): v2, 128x128 unless few tiles / a narrow or ragged N
     const bool narrow = a.Nc <= 64 || (a.Nc % 128 != 0 && a.Nc % 128 <= 64) ||
                         ((long long)((a.Mc + 127) / 128) * ((a.Nc + 127) / 128) * nz < 384);
-    // conv taps that core v2 cannot keep uniform per K-tile run on its generic-decode kernel (tile 7 only)
+    // conv taps that core v2 cannot keep uniform per K-tile run on its generic-decode kernel (one tile only)
     const bool odd_taps = a.taps > 1 && (a.shift_operand == 0 ? (p.Rper % 32) != 0 : a.T < 32);
-    tile = v2_ok ? (odd_taps ? (v1_ok && !a.operand_bf16 && !a.colsum ? 3 : 7) : (narrow ? 5 : 4)) : (narrow ? 2 : 1);  // (core v1 is fp32 only)
+    tile = v2_ok ? (odd_taps ? (v1_ok && !a.operand_bf16 && !a.colsum ? FS2_TILE_STAGED_SMALL : FS2_TILE_GENERIC_TAPS)
+                             : (narrow ? FS2_TILE_LDS_NARROW : FS2_TILE_LDS_WIDE))
+                 : (narrow ? FS2_TILE_STAGED_NARROW : FS2_TILE_STAGED_WIDE);  // (core v1 is fp32 only)
   }
-  if (a.operand_bf16 == 3 && (tile < 4 || tile > 9)) return FS2HIP_EINVAL;  // the one-tile-per-workgroup direct-to-LDS core only
-  if (tile >= 4) {
-    if (tile != 32 && !v2_ok) return FS2HIP_EINVAL;
-    route = {ROUTE_V2, tile, nz};
-    return 0;
-  }
-  if (!v1_ok || a.colsum) return FS2HIP_EINVAL;  // (the register-staged core does not sum columns)
-  route = {ROUTE_V1, tile, nz};
+  if (tile < 0) tile = FS2_TILE_STAGED_WIDE;  // (ids below the table have always run the register-staged core's widest tile)
+  const Fs2Tile* row = fs2_tile(tile);
+  if (!row || fs2_family_stored(row->family)) return FS2HIP_EINVAL;
+  if (a.operand_bf16 == 3 && row->family != FS2_TF_LDS) return FS2HIP_EINVAL;  // the one-tile-per-workgroup direct-to-LDS core only
+  if (row->family == FS2_TF_STAGED && (!v1_ok || a.colsum)) return FS2HIP_EINVAL;  // (that core does not sum columns)
+  if (row->family != FS2_TF_STAGED && row->family != FS2_TF_WS32 && !v2_ok) return FS2HIP_EINVAL;
+  route = {row, nz};
   return 0;
 }
 
-int gemm_launch(GemmP& p, const GemmRoute& route, hipStream_t s) {
-  const Fs2GemmArgs& a = p.a;
-  const int tile = route.tile, nz = route.nz;
-  if (route.core == ROUTE_B) {
-    if (tile == 33) return fs2_gemmws4_launch(p, s);
-    if (tile >= 30) return fs2_gemmws_launch(p, tile, s);
-    return fs2_gemmb_launch(p, tile, nz, s);
-  }
-  if (route.core == ROUTE_V2) {
-    if (tile == 32) return fs2_gemmws32_launch(p, s);
-    return tile >= 10 ? fs2_gemm2p_launch(p, tile, nz, s) : fs2_gemm2_launch(p, tile, nz, s);
-  }
-  if (tile == 3) {
-    p.tiles_n = (a.Nc + 63) / 64;
-    dim3 grid(((a.Mc + 63) / 64) * p.tiles_n, 1, nz);
-    gemm_kernel<64, 64><<<grid, dim3(256), 0, s>>>(p);
-  } else if (tile == 2) {
-    p.tiles_n = (a.Nc + 63) / 64;
-    dim3 grid(((a.Mc + 127) / 128) * p.tiles_n, 1, nz);
-    gemm_kernel<128, 64><<<grid, dim3(256), 0, s>>>(p);
-  } else {
-    p.tiles_n = (a.Nc + 127) / 128;
-    dim3 grid(((a.Mc + 127) / 128) * p.tiles_n, 1, nz);
-    gemm_kernel<128, 128><<<grid, dim3(256), 0, s>>>(p);
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
+template <int BM, int BN>
+int launch_staged(GemmP& p, int nz, hipStream_t s) {
+  p.r_chunk = fs2_split_chunk(p.a, BK);
+  const int tiles = fs2_set_tiles<BM, BN>(p, 1);
+  if (!tiles) return FS2HIP_EINVAL;
+  gemm_kernel<BM, BN><<<dim3(tiles, 1, nz), dim3(256), 0, s>>>(p);
+  return fs2_launched();
 }
+
 }  // namespace
 
 extern "C" int fs2hip_gemm(const Fs2GemmArgs* args, void* stream) {
@@ -370,7 +361,21 @@ extern "C" int fs2hip_gemm(const Fs2GemmArgs* args, void* stream) {
   GemmRoute route;
   const int rc = gemm_prepare(args, p, route);
   if (rc != 0) return rc;
-  return gemm_launch(p, route, (hipStream_t)stream);
+  const int tile = route.row->id, nz = route.nz;
+  hipStream_t s = (hipStream_t)stream;
+  switch (route.row->family) {
+    case FS2_TF_STAGED:
+      return fs2_tile_switch<FS2_TF_STAGED>(tile, [&](auto r) { return launch_staged<r.t.bm, r.t.bn>(p, nz, s); });
+    case FS2_TF_LDS: return fs2_gemm2_launch(p, tile, nz, s);
+    case FS2_TF_PERSIST:
+    case FS2_TF_PERSIST_TAIL: return fs2_gemm2p_launch(p, tile, nz, s);
+    case FS2_TF_B: return fs2_gemmb_launch(p, tile, nz, s);
+    case FS2_TF_BP: return fs2_gemmbp_launch(p, tile, nz, s);
+    case FS2_TF_WS_K256: return fs2_gemmws_launch(p, tile, s);
+    case FS2_TF_WS_K1024: return fs2_gemmws4_launch(p, s);
+    case FS2_TF_WS32: return fs2_gemmws32_launch(p, s);
+  }
+  return FS2HIP_EINVAL;
 }
 
 extern "C" int fs2hip_gemm_grouped(const Fs2GemmArgs* args, int n, void* stream) {
@@ -381,7 +386,7 @@ extern "C" int fs2hip_gemm_grouped(const Fs2GemmArgs* args, int n, void* stream)
   g.n = n;
   const bool stored = args[0].operand_bf16 == 4;
   int tile = args[0].tile;
-  if (tile == 0) tile = stored ? 23 : 7;
+  if (tile == 0) tile = stored ? FS2_TILE_GROUP_DEFAULT_B : FS2_TILE_GROUP_DEFAULT;
   for (int i = 0; i < n; ++i) {
     Fs2GemmArgs m = args[i];
     // one kernel instance for all members: plain (tap-free) GEMMs of one orientation and operand type, on a tile the
@@ -394,7 +399,8 @@ extern "C" int fs2hip_gemm_grouped(const Fs2GemmArgs* args, int n, void* stream)
     GemmRoute route;
     const int rc = gemm_prepare(&m, g.m[i], route);
     if (rc != 0) return rc;
-    if (route.core != (stored ? ROUTE_B : ROUTE_V2) || route.tile != tile || route.nz != g.m[i].a.splitk) return FS2HIP_EINVAL;
+    if (route.row->family != (stored ? FS2_TF_B : FS2_TF_LDS) || route.row->id != tile || route.nz != g.m[i].a.splitk)
+      return FS2HIP_EINVAL;
   }
   return stored ? fs2_gemmb_launch_grouped(g, tile, (hipStream_t)stream) : fs2_gemm2_launch_grouped(g, tile, (hipStream_t)stream);
 }

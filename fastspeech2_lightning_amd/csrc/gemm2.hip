@@ -18,6 +18,7 @@
 //  * XCD-aware workgroup order (tiles sharing an M-tile's A rows, and the tiles of one split-K / tap slice, run on
 //    one XCD's L2).
 #include "gemm2_core.h"
+#include "gemm_launch.h"
 namespace {
 
 // ``bid`` of ``nblk``: the workgroup's index inside its launch -- or, in a grouped launch, inside its member's share of it
@@ -126,112 +127,47 @@ __global__ __launch_bounds__(256) void gemm2g_kernel(GemmPG g) {
   gemm2_body<BM, BN, AKC, BKC, NST, TAPS_NONE, 0>(g.m[i], blockIdx.x - g.start[i], g.start[i + 1] - g.start[i]);
 }
 
-// fp32 or bf16-operand instance of one kernel shape
-#define FS2_GO(AKC_, BKC_, TAPS_)                                                          \
-  do {                                                                                     \
-    if (a.operand_bf16 == 2) gemm2_kernel<BM, BN, AKC_, BKC_, NST, TAPS_, 2><<<grid, block, 0, s>>>(p);  \
-    else if (a.operand_bf16) gemm2_kernel<BM, BN, AKC_, BKC_, NST, TAPS_, 1><<<grid, block, 0, s>>>(p);  \
-    else gemm2_kernel<BM, BN, AKC_, BKC_, NST, TAPS_, 0><<<grid, block, 0, s>>>(p);        \
-  } while (0)
+static_assert(TAPS_NONE == FS2_TAPS_NONE && TAPS_RED == FS2_TAPS_RED && TAPS_ROWS == FS2_TAPS_ROWS &&
+              TAPS_GENERIC == FS2_TAPS_GENERIC, "the launch helpers' tap modes are this core's TAPS arguments");
 
+// GENERIC_TOO: odd tap widths run on the generic decode, which only FS2_TILE_GENERIC_TAPS carries
 template <int BM, int BN, int NST, bool GENERIC_TOO>
 int launch_tile(GemmP& p, int nz, hipStream_t s) {
-  const Fs2GemmArgs& a = p.a;
-  p.tiles_m = (a.Mc + BM - 1) / BM;
-  p.tiles_n = (a.Nc + BN - 1) / BN;
-  if ((long long)p.tiles_m * p.tiles_n * nz > 0x7fffffffLL) return FS2HIP_EINVAL;
-  dim3 grid(p.tiles_m * p.tiles_n * nz), block(256);
-  int mode = TAPS_NONE;
-  if (a.operand_bf16 == 3 && !(a.a_kcontig && a.b_kcontig)) return FS2HIP_EINVAL;
-  if (a.taps > 1) {
-    if (a.shift_operand == 0) mode = (p.Rper % BK2 == 0) ? TAPS_RED : TAPS_GENERIC;
-    else mode = a.T >= BK2 ? TAPS_ROWS : TAPS_GENERIC;
-  }
-  if (mode == TAPS_GENERIC && a.operand_bf16 == 3) return FS2HIP_EINVAL;
-  if (mode == TAPS_GENERIC) {
-    if constexpr (GENERIC_TOO) {
-      if (a.a_kcontig && a.b_kcontig) FS2_GO(true, true, TAPS_GENERIC);
-      else if (a.a_kcontig) FS2_GO(true, false, TAPS_GENERIC);
-      else if (!a.b_kcontig) FS2_GO(false, false, TAPS_GENERIC);
-      else return FS2HIP_EINVAL;
-    } else {
-      return FS2HIP_EINVAL;  // odd tap widths: only the 64x64 2-stage tile carries the generic decode
-    }
-  } else if (a.a_kcontig && a.b_kcontig) {  // forward: taps only as TAPS_RED
-    if (a.operand_bf16 == 3) {  // bf16 in memory: these two instances only
-      if (mode == TAPS_RED) gemm2_kernel<BM, BN, true, true, NST, TAPS_RED, 3><<<grid, block, 0, s>>>(p);
-      else if (mode == TAPS_NONE) gemm2_kernel<BM, BN, true, true, NST, TAPS_NONE, 3><<<grid, block, 0, s>>>(p);
-      else return FS2HIP_EINVAL;
-    } else if (mode == TAPS_RED) FS2_GO(true, true, TAPS_RED);
-    else if (mode == TAPS_NONE) FS2_GO(true, true, TAPS_NONE);
-    else return FS2HIP_EINVAL;
-  } else if (a.a_kcontig && !a.b_kcontig) {  // backward data
-    if (mode == TAPS_RED) FS2_GO(true, false, TAPS_RED);
-    else if (mode == TAPS_NONE) FS2_GO(true, false, TAPS_NONE);
-    else return FS2HIP_EINVAL;
-  } else if (!a.a_kcontig && !a.b_kcontig) {  // weight gradient
-    if (mode == TAPS_ROWS) FS2_GO(false, false, TAPS_ROWS);
-    else if (mode == TAPS_NONE) FS2_GO(false, false, TAPS_NONE);
-    else return FS2HIP_EINVAL;
-  } else {
-    return FS2HIP_EINVAL;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
+  const int units = fs2_set_tiles<BM, BN>(p, nz);
+  if (!units) return FS2HIP_EINVAL;
+  return fs2_dispatch_fp32<GENERIC_TOO, true>(p, BK2, [&](auto akc, auto bkc, auto taps, auto bf) {
+    gemm2_kernel<BM, BN, akc, bkc, NST, taps, bf><<<dim3(units), dim3(256), 0, s>>>(p);
+    return fs2_launched();
+  });
 }
-
-#undef FS2_GO
 
 template <int BM, int BN, int NST>
 int launch_grouped(GemmPG& g, hipStream_t s) {
-  long long total = 0;
-  for (int i = 0; i < g.n; ++i) {
-    GemmP& p = g.m[i];
-    const Fs2GemmArgs& a = p.a;
-    const int chunk = (a.R + a.splitk - 1) / a.splitk;
-    p.r_chunk = ((chunk + BK2 - 1) / BK2) * BK2;
-    p.tiles_m = (a.Mc + BM - 1) / BM;
-    p.tiles_n = (a.Nc + BN - 1) / BN;
-    if (!fs2_gemm2_offsets_fit(a)) return FS2HIP_EINVAL;
-    g.start[i] = (int)total;
-    total += (long long)p.tiles_m * p.tiles_n * a.splitk;
-    if (total > 0x7fffffffLL) return FS2HIP_EINVAL;
-  }
-  for (int i = g.n; i <= FS2_GEMM_GROUP_MAX; ++i) g.start[i] = (int)total;
-  const Fs2GemmArgs& a = g.m[0].a;
-  dim3 grid((unsigned)total), block(256);
-  if (a.a_kcontig && a.b_kcontig) gemm2g_kernel<BM, BN, true, true, NST><<<grid, block, 0, s>>>(g);
-  else if (a.a_kcontig && !a.b_kcontig) gemm2g_kernel<BM, BN, true, false, NST><<<grid, block, 0, s>>>(g);
-  else if (!a.a_kcontig && !a.b_kcontig) gemm2g_kernel<BM, BN, false, false, NST><<<grid, block, 0, s>>>(g);
-  else return FS2HIP_EINVAL;
-  FS2_LAUNCH_CHECK();
-  return 0;
+  for (int i = 0; i < g.n; ++i)
+    if (!fs2_gemm2_offsets_fit(g.m[i].a)) return FS2HIP_EINVAL;
+  const int total = fs2_group_starts<BM, BN>(g, BK2);
+  if (!total) return FS2HIP_EINVAL;
+  return fs2_dispatch_orient_taps<false>(g.m[0].a, FS2_TAPS_NONE, [&](auto akc, auto bkc, auto) {
+    gemm2g_kernel<BM, BN, akc, bkc, NST><<<dim3((unsigned)total), dim3(256), 0, s>>>(g);
+    return fs2_launched();
+  });
 }
 
 }  // namespace
 
 int fs2_gemm2_launch_grouped(GemmPG& g, int tile, hipStream_t s) {
-  switch (tile) {
-    case 7: return launch_grouped<64, 64, 2>(g, s);
-    case 8: return launch_grouped<128, 64, 2>(g, s);
-    default: return FS2HIP_EINVAL;
-  }
+  return fs2_tile_switch<FS2_TF_LDS>(tile, [&](auto r) {
+    if constexpr (r.t.grouped) return launch_grouped<r.t.bm, r.t.bn, r.t.depth>(g, s);
+    else return (int)FS2HIP_EINVAL;
+  });
 }
 
 int fs2_gemm2_launch(GemmP& p, int tile, int nz, hipStream_t s) {
-  const Fs2GemmArgs& a = p.a;
   // 16-byte pieces: k-contiguous operands need Rper % 4 == 0 (checked by the caller); the reduction
   // chunk of a split must be a multiple of this core's BK
-  const int chunk = (a.R + a.splitk - 1) / a.splitk;
-  p.r_chunk = ((chunk + BK2 - 1) / BK2) * BK2;
-  if (!fs2_gemm2_offsets_fit(a)) return FS2HIP_EINVAL;  // > 2 GiB operands: core v1
-  switch (tile) {
-    case 4: return launch_tile<128, 128, 3, false>(p, nz, s);  // 96 KiB ring, 1 workgroup / CU
-    case 5: return launch_tile<128, 64, 3, false>(p, nz, s);   // 72 KiB ring, 2 workgroups / CU
-    case 6: return launch_tile<64, 64, 4, false>(p, nz, s);    // 64 KiB ring, 2 workgroups / CU
-    case 7: return launch_tile<64, 64, 2, true>(p, nz, s);     // 32 KiB, 5 workgroups / CU (occupancy instead of depth)
-    case 8: return launch_tile<128, 64, 2, false>(p, nz, s);   // 48 KiB, 3 workgroups / CU
-    case 9: return launch_tile<128, 128, 2, false>(p, nz, s);  // 64 KiB, 2 workgroups / CU
-    default: return FS2HIP_EINVAL;
-  }
+  p.r_chunk = fs2_split_chunk(p.a, BK2);
+  if (!fs2_gemm2_offsets_fit(p.a)) return FS2HIP_EINVAL;  // > 2 GiB operands: core v1
+  return fs2_tile_switch<FS2_TF_LDS>(tile, [&](auto r) {
+    return launch_tile<r.t.bm, r.t.bn, r.t.depth, r.t.id == FS2_TILE_GENERIC_TAPS>(p, nz, s);
+  });
 }

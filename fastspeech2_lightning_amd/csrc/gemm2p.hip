@@ -13,6 +13,7 @@
 // Work-unit ids go through the XCD remap, so the units that the workgroups of one XCD process in the same
 // round are consecutive tiles (shared A rows stay in that XCD's L2).
 #include "gemm2_core.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -204,29 +205,13 @@ __global__ __launch_bounds__(256) void tail_fixup_epi_kernel(GemmP p, Hybrid hy)
   }
 }
 
-#define FS2_GO(AKC_, BKC_, TAPS_)                                                                             \
-  do {                                                                                                        \
-    if (a.operand_bf16 == 2) gemm2p_kernel<BM, BN, AKC_, BKC_, TAPS_, 2><<<grid, block, 0, s>>>(p, hy, nunits, tiles);  \
-    else if (a.operand_bf16) gemm2p_kernel<BM, BN, AKC_, BKC_, TAPS_, 1><<<grid, block, 0, s>>>(p, hy, nunits, tiles);  \
-    else gemm2p_kernel<BM, BN, AKC_, BKC_, TAPS_, 0><<<grid, block, 0, s>>>(p, hy, nunits, tiles);            \
-  } while (0)
-
 template <int BM, int BN, int WG_PER_CU, bool SPLIT_TAIL>
 int launch_persistent(GemmP& p, int nz, hipStream_t s) {
   const Fs2GemmArgs& a = p.a;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return FS2HIP_EINVAL;
-    n_cu = prop.multiProcessorCount;
-  }
-  p.tiles_m = (a.Mc + BM - 1) / BM;
-  p.tiles_n = (a.Nc + BN - 1) / BN;
+  const int n_cu = fs2_cu_count();
+  int nunits = fs2_set_tiles<BM, BN>(p, nz);
+  if (!n_cu || !nunits) return FS2HIP_EINVAL;
   const int tiles = p.tiles_m * p.tiles_n;
-  const long long nunits_ll = (long long)tiles * nz;
-  if (nunits_ll > 0x7fffffffLL) return FS2HIP_EINVAL;
-  int nunits = (int)nunits_ll;
   const int slots = n_cu * WG_PER_CU;
   Hybrid hy{0, 0, 0, 0, nullptr, 0};
   if (SPLIT_TAIL) {
@@ -260,29 +245,13 @@ int launch_persistent(GemmP& p, int nz, hipStream_t s) {
     if (hy.slab * S > a.workspace_floats || (hy.slab % 4) || ((uintptr_t)a.workspace % 16)) return FS2HIP_EINVAL;
     nunits = hy.u_full + tail_tiles * S;
   }
-  dim3 grid(nunits < slots ? nunits : slots), block(256);
-  int mode = TAPS_NONE;
-  if (a.taps > 1) {
-    if (a.shift_operand == 0) mode = (p.Rper % BK2 == 0) ? TAPS_RED : TAPS_GENERIC;
-    else mode = a.T >= BK2 ? TAPS_ROWS : TAPS_GENERIC;
-  }
-  if (mode == TAPS_GENERIC) return FS2HIP_EINVAL;  // odd tap widths: gemm2.hip tile 7
-  if (a.a_kcontig && a.b_kcontig) {
-    if (mode == TAPS_RED) FS2_GO(true, true, TAPS_RED);
-    else if (mode == TAPS_NONE) FS2_GO(true, true, TAPS_NONE);
-    else return FS2HIP_EINVAL;
-  } else if (a.a_kcontig && !a.b_kcontig) {
-    if (mode == TAPS_RED) FS2_GO(true, false, TAPS_RED);
-    else if (mode == TAPS_NONE) FS2_GO(true, false, TAPS_NONE);
-    else return FS2HIP_EINVAL;
-  } else if (!a.a_kcontig && !a.b_kcontig) {
-    if (mode == TAPS_ROWS) FS2_GO(false, false, TAPS_ROWS);
-    else if (mode == TAPS_NONE) FS2_GO(false, false, TAPS_NONE);
-    else return FS2HIP_EINVAL;
-  } else {
-    return FS2HIP_EINVAL;
-  }
-  FS2_LAUNCH_CHECK();
+  const dim3 grid(nunits < slots ? nunits : slots);
+  // (odd tap widths: gemm2.hip's FS2_TILE_GENERIC_TAPS; bf16 in memory: gemm2.hip)
+  const int rc = fs2_dispatch_fp32<false, false>(p, BK2, [&](auto akc, auto bkc, auto taps, auto bf) {
+    gemm2p_kernel<BM, BN, akc, bkc, taps, bf><<<grid, dim3(256), 0, s>>>(p, hy, nunits, tiles);
+    return fs2_launched();
+  });
+  if (rc != 0) return rc;
   if (hy.S) {
     if (a.epi == FS2_EPI_STORE)
       return fs2_tail_fixup(hy.ws, hy.S, hy.slab, a.C, a.ldc, a.bias, a.alpha, hy.m_tail0, a.Mc, a.Nc, s);
@@ -295,24 +264,14 @@ int launch_persistent(GemmP& p, int nz, hipStream_t s) {
   return 0;
 }
 
-#undef FS2_GO
-
 }  // namespace
 
-// tile ids 10-12: persistent 64x64 (4 workgroups / CU), 128x64 (3), 128x128 (2); 13/14/15: 128x128 / 128x64 / 64x64 + split tail
 int fs2_gemm2p_launch(GemmP& p, int tile, int nz, hipStream_t s) {
   const Fs2GemmArgs& a = p.a;
-  const int chunk = (a.R + a.splitk - 1) / a.splitk;
-  p.r_chunk = ((chunk + BK2 - 1) / BK2) * BK2;
+  p.r_chunk = fs2_split_chunk(a, BK2);
   if ((long long)(a.splitk - 1) * p.r_chunk >= a.R) return FS2HIP_EINVAL;  // an empty split-K slice
   if (!fs2_gemm2_offsets_fit(a)) return FS2HIP_EINVAL;
-  switch (tile) {
-    case 10: return launch_persistent<64, 64, 4, false>(p, nz, s);  // 128 VGPRs: 4 waves per SIMD
-    case 11: return launch_persistent<128, 64, 3, false>(p, nz, s);
-    case 12: return launch_persistent<128, 128, 2, false>(p, nz, s);
-    case 13: return launch_persistent<128, 128, 2, true>(p, nz, s);
-    case 14: return launch_persistent<128, 64, 3, true>(p, nz, s);
-    case 15: return launch_persistent<64, 64, 4, true>(p, nz, s);
-    default: return FS2HIP_EINVAL;
-  }
+  return fs2_tile_switch<FS2_TF_PERSIST, FS2_TF_PERSIST_TAIL>(tile, [&](auto r) {
+    return launch_persistent<r.t.bm, r.t.bn, r.t.depth, r.t.family == FS2_TF_PERSIST_TAIL>(p, nz, s);
+  });
 }

@@ -1,8 +1,12 @@
 // One output tile per workgroup on the bf16-storage GEMM core (gemm_bf16_core.h): the forward and data-gradient GEMMs
 // (short reductions, whole-row stores through LDS).  The persistent form is gemm_bf16p.hip.
 #include "gemm_bf16_core.h"
+#include "gemm_launch.h"
 
 namespace {
+
+static_assert(BT_NONE == FS2_TAPS_NONE && BT_RED == FS2_TAPS_RED && BT_ROWS == FS2_TAPS_ROWS,
+              "the launch helpers' tap modes are this core's TAPS arguments");
 
 // ``bid`` of ``nblk``: the workgroup's index inside its launch -- or, in a grouped launch, inside its member's share of it
 template <int BM, int BN, bool AKC, bool BKC, int TAPS, int NST, bool COLSUM>
@@ -115,95 +119,35 @@ __global__ __launch_bounds__(256) void gemmbg_kernel(GemmPG g) {
 
 template <int BM, int BN, int NST>
 int launch_b(GemmP& p, int nz, hipStream_t s) {
-  const Fs2GemmArgs& a = p.a;
-  p.tiles_m = (a.Mc + BM - 1) / BM;
-  p.tiles_n = (a.Nc + BN - 1) / BN;
-  if ((long long)p.tiles_m * p.tiles_n * nz > 0x7fffffffLL) return FS2HIP_EINVAL;
-  dim3 grid(p.tiles_m * p.tiles_n * nz), block(256);
-  int mode = BT_NONE;
-  if (a.taps > 1) {
-    if (a.shift_operand == 0) {
-      if (p.Rper % BKE) return FS2HIP_EINVAL;
-      mode = BT_RED;
-    } else {
-      if (a.T < BKE) return FS2HIP_EINVAL;
-      mode = BT_ROWS;
-    }
-  }
-  if (a.a_kcontig && a.b_kcontig) {  // forward
-    if (mode == BT_RED) gemmb_kernel<BM, BN, true, true, BT_RED, NST, false><<<grid, block, 0, s>>>(p);
-    else if (mode == BT_NONE) gemmb_kernel<BM, BN, true, true, BT_NONE, NST, false><<<grid, block, 0, s>>>(p);
-    else return FS2HIP_EINVAL;
-  } else if (a.a_kcontig && !a.b_kcontig) {  // data gradient: the weight as it is stored, read by rows of the reduction
-    if (mode == BT_RED) gemmb_kernel<BM, BN, true, false, BT_RED, NST, false><<<grid, block, 0, s>>>(p);
-    else if (mode == BT_NONE) gemmb_kernel<BM, BN, true, false, BT_NONE, NST, false><<<grid, block, 0, s>>>(p);
-    else return FS2HIP_EINVAL;
-  } else if (!a.a_kcontig && !a.b_kcontig) {  // weight gradient (+ bias gradient)
-    if (mode == BT_ROWS) gemmb_kernel<BM, BN, false, false, BT_ROWS, NST, true><<<grid, block, 0, s>>>(p);
-    else if (mode == BT_NONE) gemmb_kernel<BM, BN, false, false, BT_NONE, NST, true><<<grid, block, 0, s>>>(p);
-    else return FS2HIP_EINVAL;
-  } else {
-    return FS2HIP_EINVAL;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
+  const int units = fs2_set_tiles<BM, BN>(p, nz);
+  if (!units) return FS2HIP_EINVAL;
+  // (forward; data gradient: the weight as it is stored, read by rows of the reduction; weight gradient + bias gradient)
+  return fs2_dispatch_orient_taps<false>(p.a, fs2_tap_mode(p, BKE, false), [&](auto akc, auto bkc, auto taps) {
+    gemmb_kernel<BM, BN, akc, bkc, taps, NST, !akc && !bkc><<<dim3(units), dim3(256), 0, s>>>(p);
+    return fs2_launched();
+  });
 }
 
 template <int BM, int BN, int NST>
 int launch_b_grouped(GemmPG& g, hipStream_t s) {
-  long long total = 0;
-  for (int i = 0; i < g.n; ++i) {
-    GemmP& p = g.m[i];
-    const Fs2GemmArgs& a = p.a;
-    const int chunk = (a.R + a.splitk - 1) / a.splitk;
-    p.r_chunk = ((chunk + BKE - 1) / BKE) * BKE;
-    p.tiles_m = (a.Mc + BM - 1) / BM;
-    p.tiles_n = (a.Nc + BN - 1) / BN;
-    g.start[i] = (int)total;
-    total += (long long)p.tiles_m * p.tiles_n * a.splitk;
-    if (total > 0x7fffffffLL) return FS2HIP_EINVAL;
-  }
-  for (int i = g.n; i <= FS2_GEMM_GROUP_MAX; ++i) g.start[i] = (int)total;
-  const Fs2GemmArgs& a = g.m[0].a;
-  dim3 grid((unsigned)total), block(256);
-  if (a.a_kcontig && a.b_kcontig) gemmbg_kernel<BM, BN, true, true, NST, false><<<grid, block, 0, s>>>(g);
-  else if (a.a_kcontig && !a.b_kcontig) gemmbg_kernel<BM, BN, true, false, NST, false><<<grid, block, 0, s>>>(g);
-  else if (!a.a_kcontig && !a.b_kcontig) gemmbg_kernel<BM, BN, false, false, NST, true><<<grid, block, 0, s>>>(g);
-  else return FS2HIP_EINVAL;
-  FS2_LAUNCH_CHECK();
-  return 0;
+  const int total = fs2_group_starts<BM, BN>(g, BKE);
+  if (!total) return FS2HIP_EINVAL;
+  return fs2_dispatch_orient_taps<false>(g.m[0].a, FS2_TAPS_NONE, [&](auto akc, auto bkc, auto) {
+    gemmbg_kernel<BM, BN, akc, bkc, NST, !akc && !bkc><<<dim3((unsigned)total), dim3(256), 0, s>>>(g);
+    return fs2_launched();
+  });
 }
 
 }  // namespace
 
 int fs2_gemmb_launch_grouped(GemmPG& g, int tile, hipStream_t s) {
-  switch (tile) {
-    case 22: return launch_b_grouped<128, 64, 2>(g, s);
-    case 23: return launch_b_grouped<64, 64, 3>(g, s);
-    case 26: return launch_b_grouped<64, 64, 2>(g, s);
-    default: return FS2HIP_EINVAL;
-  }
+  return fs2_tile_switch<FS2_TF_B>(tile, [&](auto r) {
+    if constexpr (r.t.grouped) return launch_b_grouped<r.t.bm, r.t.bn, r.t.depth>(g, s);
+    else return (int)FS2HIP_EINVAL;
+  });
 }
 
-int fs2_gemmbp_launch(GemmP& p, int tile, int nz, hipStream_t s);  // gemm_bf16p.hip
-
-// tile ids of the bf16-storage core: 20 = 128x128 (2 stages, 2 workgroups / CU), 22 = 128x64 (2 stages, 3 / CU),
-// 23 = 64x64 (3 stages, 3 / CU); persistent (one K-tile stream per workgroup across its tiles): 24 = 128x128 (2 / CU),
-// 25 = 128x64 (3 / CU).  [A deep-ring form -- one workgroup per CU, a ring of 4-5 stages with counted waits across tile
-// boundaries and epilogues -- was built, is correct, and is slower on every shape (one wavefront per SIMD cannot overlap
-// DMA issue, LDS reads, MFMAs and the epilogue): kept as tools/probes/gemm_bf16_deep_ring.hip.txt, see DESIGN.md.]
 int fs2_gemmb_launch(GemmP& p, int tile, int nz, hipStream_t s) {
-  const Fs2GemmArgs& a = p.a;
-  const int chunk = (a.R + a.splitk - 1) / a.splitk;
-  p.r_chunk = ((chunk + BKE - 1) / BKE) * BKE;
-  switch (tile) {
-    case 20: return launch_b<128, 128, 2>(p, nz, s);
-    case 21: return launch_b<128, 64, 3>(p, nz, s);  // 72 KiB: 2 workgroups / CU, two K-tiles in flight each
-    case 26: return launch_b<64, 64, 2>(p, nz, s);   // 32 KiB: 5 workgroups / CU
-    case 22: return launch_b<128, 64, 2>(p, nz, s);
-    case 23: return launch_b<64, 64, 3>(p, nz, s);
-    case 24:
-    case 25: return fs2_gemmbp_launch(p, tile, nz, s);
-    default: return FS2HIP_EINVAL;
-  }
+  p.r_chunk = fs2_split_chunk(p.a, BKE);
+  return fs2_tile_switch<FS2_TF_B>(tile, [&](auto r) { return launch_b<r.t.bm, r.t.bn, r.t.depth>(p, nz, s); });
 }

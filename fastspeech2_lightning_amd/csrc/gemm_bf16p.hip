@@ -1,6 +1,7 @@
 // Persistent form of the bf16-storage GEMM core (gemm_bf16_core.h): the weight-gradient GEMMs (long reductions cut into
 // split-K slices, fp32 slabs) and the PostNet convolutions.
 #include "gemm_bf16_core.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -106,57 +107,20 @@ __global__ __launch_bounds__(256) void gemmbp_kernel(GemmP p, int nunits, int ti
 
 template <int BM, int BN, int WG_PER_CU>
 int launch_bp(GemmP& p, int nz, hipStream_t s) {
-  const Fs2GemmArgs& a = p.a;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return FS2HIP_EINVAL;
-    n_cu = prop.multiProcessorCount;
-  }
-  p.tiles_m = (a.Mc + BM - 1) / BM;
-  p.tiles_n = (a.Nc + BN - 1) / BN;
-  const int tiles = p.tiles_m * p.tiles_n;
-  const long long nunits_ll = (long long)tiles * nz;
-  if (nunits_ll > 0x7fffffffLL) return FS2HIP_EINVAL;
-  const int nunits = (int)nunits_ll;
-  const int slots = n_cu * WG_PER_CU;
-  dim3 grid(nunits < slots ? nunits : slots), block(256);
-  int mode = BT_NONE;
-  if (a.taps > 1) {
-    if (a.shift_operand == 0) {
-      if (p.Rper % BKE) return FS2HIP_EINVAL;
-      mode = BT_RED;
-    } else {
-      if (a.T < BKE) return FS2HIP_EINVAL;
-      mode = BT_ROWS;
-    }
-  }
-  if (a.a_kcontig && a.b_kcontig) {
-    if (mode == BT_RED) gemmbp_kernel<BM, BN, true, true, BT_RED, false><<<grid, block, 0, s>>>(p, nunits, tiles);
-    else if (mode == BT_NONE) gemmbp_kernel<BM, BN, true, true, BT_NONE, false><<<grid, block, 0, s>>>(p, nunits, tiles);
-    else return FS2HIP_EINVAL;
-  } else if (a.a_kcontig && !a.b_kcontig) {
-    if (mode == BT_RED) gemmbp_kernel<BM, BN, true, false, BT_RED, false><<<grid, block, 0, s>>>(p, nunits, tiles);
-    else if (mode == BT_NONE) gemmbp_kernel<BM, BN, true, false, BT_NONE, false><<<grid, block, 0, s>>>(p, nunits, tiles);
-    else return FS2HIP_EINVAL;
-  } else if (!a.a_kcontig && !a.b_kcontig) {
-    if (mode == BT_ROWS) gemmbp_kernel<BM, BN, false, false, BT_ROWS, true><<<grid, block, 0, s>>>(p, nunits, tiles);
-    else if (mode == BT_NONE) gemmbp_kernel<BM, BN, false, false, BT_NONE, true><<<grid, block, 0, s>>>(p, nunits, tiles);
-    else return FS2HIP_EINVAL;
-  } else {
-    return FS2HIP_EINVAL;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
+  const int n_cu = fs2_cu_count();
+  const int nunits = fs2_set_tiles<BM, BN>(p, nz);
+  if (!n_cu || !nunits) return FS2HIP_EINVAL;
+  const int tiles = p.tiles_m * p.tiles_n, slots = n_cu * WG_PER_CU;
+  const dim3 grid(nunits < slots ? nunits : slots);
+  return fs2_dispatch_orient_taps<false>(p.a, fs2_tap_mode(p, BKE, false), [&](auto akc, auto bkc, auto taps) {
+    gemmbp_kernel<BM, BN, akc, bkc, taps, !akc && !bkc><<<grid, dim3(256), 0, s>>>(p, nunits, tiles);
+    return fs2_launched();
+  });
 }
 
 }  // namespace
 
 int fs2_gemmbp_launch(GemmP& p, int tile, int nz, hipStream_t s) {
-  switch (tile) {
-    case 24: return launch_bp<128, 128, 2>(p, nz, s);
-    case 25: return launch_bp<128, 64, 3>(p, nz, s);
-    default: return FS2HIP_EINVAL;
-  }
+  p.r_chunk = fs2_split_chunk(p.a, BKE);
+  return fs2_tile_switch<FS2_TF_BP>(tile, [&](auto r) { return launch_bp<r.t.bm, r.t.bn, r.t.depth>(p, nz, s); });
 }

@@ -267,24 +267,19 @@ __device__ __forceinline__ int fs2_xcd_remap(int orig, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
 }
 
-// v2 core launcher (gemm2.hip); tile: 4 = 128x128 (3-stage ring), 5 = 128x64 (3), 6 = 64x64 (4),
-// 7 = 64x64 (2), 8 = 128x64 (2), 9 = 128x128 (2)
-int fs2_gemm2_launch(GemmP& p, int tile, int nz, hipStream_t s);
-// persistent v2 core (gemm2p.hip); tile: 10 = 64x64, 11 = 128x64, 12 = 128x128 (all 2-stage); 13 / 14 = 128x128 /
-// 128x64 with the last partial round of tiles cut along the reduction
-int fs2_gemm2p_launch(GemmP& p, int tile, int nz, hipStream_t s);
-// bf16-storage core (gemm_bf16.hip / gemm_bf16p.hip); tile: 20 = 128x128, 22 = 128x64, 23 = 64x64, 24 / 25 = persistent
-// 128x128 / 128x64
-int fs2_gemmb_launch(GemmP& p, int tile, int nz, hipStream_t s);
-// weights-stationary streaming form of the bf16-storage core (gemm_ws.hip): forward orientation, K = 256; tile 30 / 31 =
-// 512 / 256 output columns per workgroup
+// The launchers of the kernel families (which tile ids each takes, and with which geometry: gemm_tiles.h); `nz`: the
+// reduction / tap slices of the launch.  FS2HIP_EINVAL: this family or tile does not take the launch.
+int fs2_gemm2_launch(GemmP& p, int tile, int nz, hipStream_t s);    // direct-to-LDS core, one tile per workgroup (gemm2.hip)
+int fs2_gemm2p_launch(GemmP& p, int tile, int nz, hipStream_t s);   // the same core, persistent (gemm2p.hip)
+int fs2_gemmb_launch(GemmP& p, int tile, int nz, hipStream_t s);    // bf16-storage core, one tile per workgroup (gemm_bf16.hip)
+int fs2_gemmbp_launch(GemmP& p, int tile, int nz, hipStream_t s);   // bf16-storage core, persistent (gemm_bf16p.hip)
+// weights-stationary streaming forms, forward orientation: bf16-storage core K = 256 (gemm_ws.hip) and K = 1024
+// (gemm_ws4.hip), exact fp32 K = 256 (gemm_ws32.hip)
 int fs2_gemmws_launch(GemmP& p, int tile, hipStream_t s);
-// the same structure in exact fp32 (gemm_ws32.hip): tile 32
-int fs2_gemmws32_launch(GemmP& p, hipStream_t s);
-// bf16-storage core, K = 1024, tile id 33 (gemm_ws4.hip)
 int fs2_gemmws4_launch(GemmP& p, hipStream_t s);
-// grouped forms (GemmPG): fp32 core tiles 7 / 8, bf16-storage core tiles 22 / 23 / 26; every member prepared by
-// fs2hip_gemm's own checks (p.a, Rper, drop, staged set; tiles_m / tiles_n / r_chunk / start are filled in here)
+int fs2_gemmws32_launch(GemmP& p, hipStream_t s);
+// grouped forms (GemmPG) on the rows of gemm_tiles.h marked `grouped`; every member prepared by fs2hip_gemm's own
+// checks (p.a, Rper, drop, staged set; tiles_m / tiles_n / r_chunk / start are filled in here)
 int fs2_gemm2_launch_grouped(GemmPG& g, int tile, hipStream_t s);
 int fs2_gemmb_launch_grouped(GemmPG& g, int tile, hipStream_t s);
 // finishes the reduction-split tail tiles of a persistent launch (reduce.hip)

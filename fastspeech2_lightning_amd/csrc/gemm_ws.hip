@@ -24,6 +24,7 @@
 #include <type_traits>
 
 #include "gemm_bf16_core.h"
+#include "gemm_launch.h"
 #include "gemm_ws_util.h"
 
 namespace {
@@ -368,25 +369,12 @@ __global__ __launch_bounds__(WS_THREADS, (NB == 1 && OBF) ? 4 : 2) void gemmws_k
 template <int NB>
 int launch_ws(GemmP& p, hipStream_t s) {
   const Fs2GemmArgs& a = p.a;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return FS2HIP_EINVAL;
-    n_cu = prop.multiProcessorCount;
-  }
-  const int n_slices = (a.Nc + 256 * NB - 1) / (256 * NB);
   // 32 columns per wavefront with bf16 results: 128 registers and 70 KB of LDS -- two workgroups per CU (four wavefronts
   // per SIMD: the LDS round trips and the arithmetic of one hide under the others')
-  const int wgs_per_cu = (NB == 1 && (a.io_bf16 & 1)) ? 2 : 1;
-  const int per_xcd = n_cu / 8 * wgs_per_cu;
-  if (per_xcd < 1 || n_slices > per_xcd) return FS2HIP_EINVAL;
-  const int n_row_tiles = (a.Mc + 31) / 32;
-  int streams_per_xcd = per_xcd / n_slices;
-  // few rows: no more streams than row tiles
-  while (streams_per_xcd > 1 && (streams_per_xcd - 1) * 8 >= n_row_tiles) --streams_per_xcd;
-  const int n_streams = streams_per_xcd * 8;
-  dim3 grid(8 * streams_per_xcd * n_slices), block(WS_THREADS);
+  Fs2WsGrid g;
+  if (!fs2_ws_grid(a, 256 * NB, (NB == 1 && (a.io_bf16 & 1)) ? 2 : 1, g)) return FS2HIP_EINVAL;
+  const int n_slices = g.n_slices, n_streams = g.n_streams, n_row_tiles = g.n_row_tiles;
+  const dim3 grid(g.blocks), block(WS_THREADS);
   const bool obf = (a.io_bf16 & 1) != 0, auxb = (a.io_bf16 & 2) != 0, two = a.out_pre != nullptr;
   // 64 columns per wavefront hold 128 registers of W: the instances that also carry operand quads or a second fp32
   // output do not fit the 256 registers of two wavefronts per SIMD (they would spill, and scratch traffic is
@@ -430,8 +418,8 @@ int launch_ws(GemmP& p, hipStream_t s) {
 
 }  // namespace
 
-// tile ids 30 / 31: 64 / 32 output columns per wavefront (512 / 256 per workgroup).  Takes: forward orientation (both
-// operands k-contiguous bf16), K = 256, no conv taps, no split, whole 16-byte chunks in every output row.
+// 64 / 32 output columns per wavefront (512 / 256 per workgroup).  Takes: forward orientation (both operands
+// k-contiguous bf16), K = 256, no conv taps, no split, whole 16-byte chunks in every output row.
 int fs2_gemmws_launch(GemmP& p, int tile, hipStream_t s) {
   const Fs2GemmArgs& a = p.a;
   if (!a.a_kcontig || !a.b_kcontig || a.taps != 1 || a.splitk != 1 || a.R != 64 * WS_KT || a.colsum) return FS2HIP_EINVAL;
@@ -440,9 +428,5 @@ int fs2_gemmws_launch(GemmP& p, int tile, hipStream_t s) {
   if (a.out_pre && (a.epi != FS2_EPI_ACT || a.ldpre != a.ldc || ((uintptr_t)a.out_pre % 16))) return FS2HIP_EINVAL;
   if ((long long)(a.Mc + 64) * a.lda * 2 >= 0x7fffffffLL || (long long)(a.Nc + 64) * a.ldb * 2 >= 0x7fffffffLL) return FS2HIP_EINVAL;
   if ((long long)(a.Mc + 64) * a.ldc * 4 >= 0x7fffffffLL) return FS2HIP_EINVAL;
-  switch (tile) {
-    case 30: return launch_ws<2>(p, s);
-    case 31: return launch_ws<1>(p, s);
-    default: return FS2HIP_EINVAL;
-  }
+  return fs2_tile_switch<FS2_TF_WS_K256>(tile, [&](auto r) { return launch_ws<r.t.bn / 256>(p, s); });
 }

@@ -29,6 +29,7 @@
 // barrier per tile, same stage discipline (at barrier i every wavefront has finished READING tile i - 1), same
 // arithmetic in the same order: still bit-identical to the tiled kernels.
 #include "gemm2_core.h"
+#include "gemm_launch.h"
 
 namespace {
 
@@ -141,7 +142,7 @@ int go32(GemmP& p, dim3 grid, int n_slices, int n_streams, int n_row_tiles, hipS
 
 }  // namespace
 
-// tile id 32: exact fp32, forward orientation (both operands k-contiguous), K = 256, no conv taps, no split
+// family FS2_TF_WS32: exact fp32, forward orientation (both operands k-contiguous), K = 256, no conv taps, no split
 int fs2_gemmws32_launch(GemmP& p, hipStream_t s) {
   const Fs2GemmArgs& a = p.a;
   if (a.operand_bf16 != 0 || !a.a_kcontig || !a.b_kcontig || a.taps != 1 || a.splitk != 1 || a.R != 256 || a.colsum)
@@ -149,21 +150,10 @@ int fs2_gemmws32_launch(GemmP& p, hipStream_t s) {
   if ((a.ldb % 4) || ((uintptr_t)a.B % 16) || a.epi < FS2_EPI_STORE || a.epi > FS2_EPI_DACT) return FS2HIP_EINVAL;
   if (a.out_pre && a.epi != FS2_EPI_ACT) return FS2HIP_EINVAL;
   if ((long long)(a.Mc + 64) * a.lda * 4 >= 0x7fffffffLL) return FS2HIP_EINVAL;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return FS2HIP_EINVAL;
-    n_cu = prop.multiProcessorCount;
-  }
-  const int n_slices = (a.Nc + 255) / 256;
-  const int per_xcd = n_cu / 8;
-  if (per_xcd < 1 || n_slices > per_xcd) return FS2HIP_EINVAL;
-  const int n_row_tiles = (a.Mc + 31) / 32;
-  int streams_per_xcd = per_xcd / n_slices;
-  while (streams_per_xcd > 1 && (streams_per_xcd - 1) * 8 >= n_row_tiles) --streams_per_xcd;
-  const int n_streams = streams_per_xcd * 8;
-  dim3 grid(8 * streams_per_xcd * n_slices);
+  Fs2WsGrid g;
+  if (!fs2_ws_grid(a, 256, 1, g)) return FS2HIP_EINVAL;
+  const int n_slices = g.n_slices, n_streams = g.n_streams, n_row_tiles = g.n_row_tiles;
+  const dim3 grid(g.blocks);
   switch (a.epi) {
     case FS2_EPI_ACT: return go32<FS2_EPI_ACT>(p, grid, n_slices, n_streams, n_row_tiles, s);
     case FS2_EPI_RESID: return go32<FS2_EPI_RESID>(p, grid, n_slices, n_streams, n_row_tiles, s);

@@ -23,6 +23,7 @@
 // not what a single wavefront per SIMD fails to overlap.)
 // Epilogues, dropout masks and rounding are those of gemm_bf16_core.h, element for element.
 #include "gemm_bf16_core.h"
+#include "gemm_launch.h"
 #include "gemm_ws_util.h"
 
 namespace {
@@ -274,7 +275,7 @@ void go4(GemmP& p, dim3 grid, int n_slices, int n_streams, int n_row_tiles, hipS
 
 }  // namespace
 
-// tile id 33: forward orientation (both operands k-contiguous bf16), K = 1024, no conv taps, no split, store or
+// family FS2_TF_WS_K1024: forward orientation (both operands k-contiguous bf16), K = 1024, no conv taps, no split, store or
 // residual epilogue, whole 16-byte chunks in every output row
 int fs2_gemmws4_launch(GemmP& p, hipStream_t s) {
   const Fs2GemmArgs& a = p.a;
@@ -288,21 +289,10 @@ int fs2_gemmws4_launch(GemmP& p, hipStream_t s) {
   if (a.epi == FS2_EPI_RESID && ((a.ldr % 4) || ((uintptr_t)a.resid % 16))) return FS2HIP_EINVAL;
   if ((long long)(a.Mc + 64) * a.lda * 2 >= 0x7fffffffLL || (long long)(a.Nc + 64) * a.ldb * 2 >= 0x7fffffffLL) return FS2HIP_EINVAL;
   if ((long long)(a.Mc + 64) * a.ldc * 4 >= 0x7fffffffLL || (long long)(a.Mc + 64) * a.ldr * 4 >= 0x7fffffffLL) return FS2HIP_EINVAL;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return FS2HIP_EINVAL;
-    n_cu = prop.multiProcessorCount;
-  }
-  const int n_slices = (a.Nc + 127) / 128;
-  const int per_xcd = n_cu / 8;  // one workgroup per CU (150 KB of LDS, 512 registers per lane)
-  if (per_xcd < 1 || n_slices > per_xcd) return FS2HIP_EINVAL;
-  const int n_row_tiles = (a.Mc + 31) / 32;
-  int streams_per_xcd = per_xcd / n_slices;
-  while (streams_per_xcd > 1 && (streams_per_xcd - 1) * 8 >= n_row_tiles) --streams_per_xcd;
-  const int n_streams = streams_per_xcd * 8;
-  dim3 grid(8 * streams_per_xcd * n_slices);
+  Fs2WsGrid g;  // one workgroup per CU (150 KB of LDS, 512 registers per lane)
+  if (!fs2_ws_grid(a, 128, 1, g)) return FS2HIP_EINVAL;
+  const int n_slices = g.n_slices, n_streams = g.n_streams, n_row_tiles = g.n_row_tiles;
+  const dim3 grid(g.blocks);
   if (a.epi == FS2_EPI_RESID) {
     if (obf) go4<FS2_EPI_RESID, true>(p, grid, n_slices, n_streams, n_row_tiles, s);
     else go4<FS2_EPI_RESID, false>(p, grid, n_slices, n_streams, n_row_tiles, s);

@@ -407,14 +407,10 @@ def get_precision() -> str:
     return {0: "32-true", 1: "bf16-mixed", 2: "32-split"}[int(GEMM_BF16)]
 
 
-GEMM_TILES_B = (20, 21, 22, 23, 24, 25, 26, 30, 31, 33)  # bf16-storage core (operand_bf16 == 4): 128x128, 128x64, 64x64;
-#                                      24 / 25: persistent 128x128 / 128x64; 30 / 31: weights-stationary streaming form
-#                                      (K = 256, forward orientation: csrc/gemm_ws.hip), 512 / 256 columns per workgroup;
-#                                      33: the same for K = 1024 (csrc/gemm_ws4.hip), 128 columns per workgroup
-GEMM_TILES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 32)  # 1-3: register-staged BK=16 core; 4-9: direct-to-LDS BK=32 core;
-#                                                      10-12: persistent direct-to-LDS core; 13-15: + split tail;
-#                                                      32: weights-stationary streaming form (exact fp32, K = 256, forward
-#                                                      orientation: csrc/gemm_ws32.hip)
+#: tile ids the tuner tries, bf16 operands in memory (operand_bf16 == 4) / fp32 operands: the rows of csrc/gemm_tiles.h,
+#: which says what each id is (checked by tests/test_gemm_tiles_cpu.py)
+GEMM_TILES_B = (20, 21, 22, 23, 24, 25, 26, 30, 31, 33)
+GEMM_TILES = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 32)
 #: FS2_GEMM_EXCLUDE_TILES=33,30 (measurement aid): tile ids the tuner leaves out -- same-box A/B runs of a kernel family
 _EXCLUDED = {int(t) for t in os.environ.get("FS2_GEMM_EXCLUDE_TILES", "").split(",") if t.strip()}
 if _EXCLUDED:
@@ -720,7 +716,7 @@ def _profile_gemm(a, e0, e1, members=None):
 #: FS2_GEMM_GROUP=0 (measurement aid): ``gemm_group()`` sections launch their GEMMs one by one, as before round 5
 GEMM_GROUP = os.environ.get("FS2_GEMM_GROUP", "1") != "0"
 GROUP_MAX = 8  # FS2_GEMM_GROUP_MAX (include/fs2hip.h)
-#: tiles the grouped kernels are built for, first = default: fp32 core / bf16-storage core (csrc/gemm2.hip, gemm_bf16.hip)
+#: tiles the grouped kernels are built for, first = default: fp32 / bf16-storage operands (the `grouped` rows of csrc/gemm_tiles.h)
 GROUP_TILES = {0: (7, 8), 4: (23, 26, 22)}
 _GROUP = None
 _GROUP_TILE_CACHE = {}
