@@ -10,6 +10,7 @@
 // directly the B operand of the next MFMA (any k-order is a valid reduction order for fp32).
 #include "attention2.h"
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -553,21 +554,20 @@ __global__ __launch_bounds__(256) void attn_unpad_heads_kernel(const float* __re
 
 }  // namespace
 
-#define ATTN_DISPATCH_HD(HD_, CALL)                     \
-  switch (HD_) {                                        \
-    case 16: { constexpr int HDc = 16; CALL; } break;   \
-    case 32: { constexpr int HDc = 32; CALL; } break;   \
-    case 64: { constexpr int HDc = 64; CALL; } break;   \
-    case 128: { constexpr int HDc = 128; CALL; } break; \
-    default: { constexpr int HDc = 256; CALL; } break;  \
-  }
-#define ATTN_DISPATCH(HD_, BF_, CALL)                              \
-  if (BF_) { constexpr bool BFc = true; ATTN_DISPATCH_HD(HD_, CALL) } \
-  else { constexpr bool BFc = false; ATTN_DISPATCH_HD(HD_, CALL) }
-
 // The launchers behind the entry points.  HDk: the head width the tensors are laid out in and the kernels run at (16, 32,
 // 64, 128 or 256); scale: 1/sqrt(true head dimension) -- 1/sqrt(HDk) except on the zero-padded route.
 namespace {
+
+// The first-generation kernels' constants: f(hd, bf) with the head width the kernels run at (16, 32, 64, 128, or 256:
+// fs2hip_attention_padded_dim) and operands rounded to bf16 or not; their grid is (row block of 64, head, utterance).
+template <class F>
+int attn_pick(int HDk, bool operands_bf16, F&& f) {
+  return fs2_pick_int<256, 16, 32, 64, 128>(HDk, [&](auto hd) {
+    return fs2_pick_bool(operands_bf16, [&](auto bf) { return f(hd, bf); });
+  });
+}
+dim3 attn_grid(int B, int T, int H) { return dim3((T + 63) / 64, H, B); }
+
 
 int attn_fwd_run(const float* qkv, const int* lens, float* o, float* lse, int B, int T, int H, int HDk, float scale,
                  Fs2Drop drop, int operand_bf16, hipStream_t s) {
@@ -576,10 +576,10 @@ int attn_fwd_run(const float* qkv, const int* lens, float* o, float* lse, int B,
     return fs2_attn2_fwd(a2, o, lse, s);
   }
   AttnP p{qkv, lens, B, T, H, scale, drop};
-  dim3 grid((T + 63) / 64, H, B);
-  ATTN_DISPATCH(HDk, operand_bf16 == 1, (attn_fwd_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, o, lse)));
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return attn_pick(HDk, operand_bf16 == 1, [&](auto hd, auto bf) {
+    attn_fwd_kernel<hd, bf><<<attn_grid(B, T, H), dim3(256), 0, s>>>(p, o, lse);
+    return fs2_launched();
+  });
 }
 
 int attn_fwd_s_run(const float* qkv, const int* lens, float* o, float* lse, float* scores, long long score_floats, int B,
@@ -599,12 +599,12 @@ int attn_bwd_run(const float* qkv, const int* lens, const float* o, const float*
   attn_delta_kernel<<<dim3((B * T + 3) / 4), dim3(256), 0, s>>>(dout, o, delta, B, T, H, HDk);
   FS2_LAUNCH_CHECK();
   AttnP p{qkv, lens, B, T, H, scale, drop};
-  dim3 grid((T + 63) / 64, H, B);
-  ATTN_DISPATCH(HDk, operand_bf16 == 1, (attn_bwd_dq_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, dout, lse, delta, dqkv)));
-  FS2_LAUNCH_CHECK();
-  ATTN_DISPATCH(HDk, operand_bf16 == 1, (attn_bwd_dkv_kernel<HDc, BFc><<<grid, dim3(256), 0, s>>>(p, dout, lse, delta, dqkv)));
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return attn_pick(HDk, operand_bf16 == 1, [&](auto hd, auto bf) {
+    attn_bwd_dq_kernel<hd, bf><<<attn_grid(B, T, H), dim3(256), 0, s>>>(p, dout, lse, delta, dqkv);
+    FS2_LAUNCH_CHECK();
+    attn_bwd_dkv_kernel<hd, bf><<<attn_grid(B, T, H), dim3(256), 0, s>>>(p, dout, lse, delta, dqkv);
+    return fs2_launched();
+  });
 }
 
 // scores: null (the dK/dV kernel recomputes K.Q^T) or the ones fs2hip_attention_fwd kept

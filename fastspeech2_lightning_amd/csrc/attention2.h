@@ -12,6 +12,19 @@ struct Attn2Args {
   long long* stamps;  // diagnostic builds only (-DFS2_ATTN_STAMPS, tools/probes/attn2_probe.hip): per-phase cycle sums
 };
 
+// Host-side bounds and grid shared by the launchers of both kernel families.
+// The dropout element index is 32 bits wide; the mask's rows are padded to an even length (one hash serves two neighbouring
+// keys), so the index stride is T + (T & 1) -- the same bound in every forward and backward launcher.
+inline bool fs2_attn_drop_index_ok(const Attn2Args& a) {
+  return (double)a.B * a.H * a.T * (a.T + (a.T & 1)) < 4294967296.0;
+}
+// One (utterance, head) slab of kept scores or spilled dS -- T rows of T rounded up to 32 elements -- per buffer resource.
+inline bool fs2_attn_slab_ok(int T, size_t elem_bytes) {
+  return (long long)T * ((T + 31) & ~31) * (long long)elem_bytes < 0x7fffffffLL;
+}
+// One workgroup per (block of `rows` query or key rows, head, utterance).
+inline dim3 fs2_attn_grid(const Attn2Args& a, int rows = 64) { return dim3(((a.T + rows - 1) / rows) * a.H * a.B); }
+
 // true when the second-generation kernels take the shape (HD in {64, 128}; operand_bf16: 0 fp32, 1 bf16, 2 split)
 bool fs2_attn2_supported(int HD, int operand_bf16);
 // s_out (fp32 MFMA path, may be null): the masked scores for fs2_attn2_bwd_spill's s_in, B * H * T * (T rounded up to 32) floats

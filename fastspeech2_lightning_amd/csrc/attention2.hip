@@ -24,6 +24,7 @@
 
 #include "gemm2_core.h"
 #include "attention_util.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -1198,63 +1199,66 @@ __global__ __launch_bounds__(256, 1) void attn2_bwd_dkv_kernel(Attn2Args p, cons
   }
 }
 
+// The launchers' constants.  Head dimension (64, or 128: fs2_attn2_supported) and dropout: f(hd, drop).
+template <class F>
+int attn2_pick(const Attn2Args& a, F&& f) {
+  return fs2_pick_int<64, 128>(a.HD, [&](auto hd) { return fs2_pick_bool(a.drop.on, [&](auto drop) { return f(hd, drop); }); });
+}
+// Operand planes: f(planes) with 1 ("bf16-mixed"), 3 ("32-split") or 0 (fp32 MFMAs: every other value).
+template <class F>
+int attn2_pick_planes(int planes, F&& f) {
+  return fs2_pick_int<0, 1, 3>(planes, f);
+}
+// ... of the backward's dK/dV kernel beside a dQ kernel on `planes`.  "32-split": dQ on the bf16 pipe (237 vs 277 us at the
+// decoder's shape), dK/dV stays on the fp32 MFMAs -- with one wavefront per SIMD its cut arithmetic (two gradient tiles per
+// step) is not hidden and the split version is slower (430 vs 340 us).  "bf16-mixed": everything on the bf16 pipe.
+constexpr int attn2_dkv_planes(int planes) { return planes == 1 ? 1 : 0; }
+
+// {lse', delta'} per row and head into aux, ahead of either form of the backward
+int attn2_prep(const Attn2Args& a, const float* o, const float* dout, const float* lse, float* aux, hipStream_t s) {
+  const float dscale = a.drop.on ? a.drop.scale : 1.f;
+  attn2_prep_kernel<<<dim3((a.B * a.T + 3) / 4), dim3(256), 0, s>>>(dout, o, lse, reinterpret_cast<float2*>(aux), a.B, a.T,
+                                                                     a.H, a.HD, log2f(dscale), 1.f / dscale);
+  return fs2_launched();
+}
+
 }  // namespace
 
 bool fs2_attn2_supported(int HD, int operand_bf16) { return (operand_bf16 >= 0 && operand_bf16 <= 2) && (HD == 64 || HD == 128); }
 
 int fs2_attn2_fwd(const Attn2Args& a, float* o, float* lse, hipStream_t s, float* s_out) {
-  // 32-bit dropout element index; the mask's rows are padded to an even length (one hash serves two neighbouring keys),
-  // so the index stride is T + (T & 1) -- the same bound in the forward and the backward launcher
-  if ((double)a.B * a.H * a.T * (a.T + (a.T & 1)) >= 4294967296.0) return FS2HIP_EINVAL;
-  dim3 grid(((a.T + 63) / 64) * a.H * a.B);
-  if (s_out && (a.planes == 1 || (long long)a.T * ((a.T + 31) & ~31) * 4 >= 0x7fffffffLL)) return FS2HIP_EINVAL;
-#define FS2_ATTN2_FWD(HD_, DROP_)                                                                 \
-  if (a.planes == 3 && s_out) attn2_fwd_kernel<HD_, DROP_, 3, true><<<grid, dim3(256), 0, s>>>(a, o, lse, s_out); \
-  else if (a.planes == 3) attn2_fwd_kernel<HD_, DROP_, 3><<<grid, dim3(256), 0, s>>>(a, o, lse);    \
-  else if (a.planes == 1) attn2_fwd_kernel<HD_, DROP_, 1><<<grid, dim3(256), 0, s>>>(a, o, lse);    \
-  else if (s_out) attn2_fwd_kernel<HD_, DROP_, 0, true><<<grid, dim3(256), 0, s>>>(a, o, lse, s_out); \
-  else attn2_fwd_kernel<HD_, DROP_, 0><<<grid, dim3(256), 0, s>>>(a, o, lse);
-  if (a.HD == 128) {
-    if (a.drop.on) { FS2_ATTN2_FWD(128, true) } else { FS2_ATTN2_FWD(128, false) }
-  } else {
-    if (a.drop.on) { FS2_ATTN2_FWD(64, true) } else { FS2_ATTN2_FWD(64, false) }
-  }
-#undef FS2_ATTN2_FWD
-  FS2_LAUNCH_CHECK();
-  return 0;
+  if (!fs2_attn_drop_index_ok(a)) return FS2HIP_EINVAL;
+  // kept scores: written by the fp32-accurate paths only, one (utterance, head) slab per buffer resource
+  if (s_out && (a.planes == 1 || !fs2_attn_slab_ok(a.T, sizeof(float)))) return FS2HIP_EINVAL;
+  return attn2_pick(a, [&](auto hd, auto drop) {
+    return attn2_pick_planes(a.planes, [&](auto planes) {
+      return fs2_pick_bool(s_out != nullptr, [&](auto scores) {
+        if constexpr (planes == 1 && scores) {
+          return (int)FS2HIP_EINVAL;
+        } else {
+          attn2_fwd_kernel<hd, drop, planes, scores><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, o, lse, s_out);
+          return fs2_launched();
+        }
+      });
+    });
+  });
 }
 
 // `delta` is the caller's [B][H][T] scratch of the first-generation interface; the second generation needs a
 // {lse', delta'} pair per row and head plus one pair of slack, so it is only used when the caller passes `aux`.
 int fs2_attn2_bwd(const Attn2Args& a, const float* o, const float* dout, const float* lse, float* aux, float* dqkv,
                   hipStream_t s) {
-  if ((double)a.B * a.H * a.T * (a.T + (a.T & 1)) >= 4294967296.0) return FS2HIP_EINVAL;
-  const float dscale = a.drop.on ? a.drop.scale : 1.f;
-  attn2_prep_kernel<<<dim3((a.B * a.T + 3) / 4), dim3(256), 0, s>>>(dout, o, lse, reinterpret_cast<float2*>(aux), a.B, a.T,
-                                                                     a.H, a.HD, log2f(dscale), 1.f / dscale);
-  FS2_LAUNCH_CHECK();
-  dim3 grid(((a.T + 63) / 64) * a.H * a.B);
+  if (!fs2_attn_drop_index_ok(a)) return FS2HIP_EINVAL;
+  if (const int rc = attn2_prep(a, o, dout, lse, aux, s)) return rc;
   const float2* ax = reinterpret_cast<const float2*>(aux);
-// "32-split": dQ on the bf16 pipe (237 vs 277 us at the decoder's shape), dK/dV stays on the fp32 MFMAs -- with one
-// wavefront per SIMD its cut arithmetic (two gradient tiles per step) is not hidden and the split version is slower
-// (430 vs 340 us).  "bf16-mixed": everything on the bf16 pipe.
-#define FS2_ATTN2_BWD_PL(HD_, DROP_, PQ_, PKV_)                                                \
-  attn2_bwd_dq_kernel<HD_, DROP_, PQ_><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv);          \
-  FS2_LAUNCH_CHECK();                                                                          \
-  attn2_bwd_dkv_kernel<HD_, DROP_, PKV_><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv);
-#define FS2_ATTN2_BWD(HD_, DROP_)                                     \
-  if (a.planes == 3) { FS2_ATTN2_BWD_PL(HD_, DROP_, 3, 0) }           \
-  else if (a.planes == 1) { FS2_ATTN2_BWD_PL(HD_, DROP_, 1, 1) }      \
-  else { FS2_ATTN2_BWD_PL(HD_, DROP_, 0, 0) }
-  if (a.HD == 128) {
-    if (a.drop.on) { FS2_ATTN2_BWD(128, true) } else { FS2_ATTN2_BWD(128, false) }
-  } else {
-    if (a.drop.on) { FS2_ATTN2_BWD(64, true) } else { FS2_ATTN2_BWD(64, false) }
-  }
-#undef FS2_ATTN2_BWD_PL
-#undef FS2_ATTN2_BWD
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return attn2_pick(a, [&](auto hd, auto drop) {
+    return attn2_pick_planes(a.planes, [&](auto planes) {
+      attn2_bwd_dq_kernel<hd, drop, planes><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, dout, ax, dqkv);
+      FS2_LAUNCH_CHECK();
+      attn2_bwd_dkv_kernel<hd, drop, attn2_dkv_planes(planes)><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, dout, ax, dqkv);
+      return fs2_launched();
+    });
+  });
 }
 
 // The backward pass with dS spilled by the dK/dV kernel and dQ as a product of its own (fp32 MFMA path only: the caller
@@ -1266,44 +1270,30 @@ long long fs2_attn2_bwd_spill_elems(const Attn2Args& a) {
 }
 int fs2_attn2_bwd_spill(const Attn2Args& a, const float* o, const float* dout, const float* lse, float* aux, float* ds,
                         float* dqkv, hipStream_t s, const float* s_in) {
-  if ((double)a.B * a.H * a.T * (a.T + (a.T & 1)) >= 4294967296.0 || fs2_attn2_bwd_spill_elems(a) == 0) return FS2HIP_EINVAL;
-  if ((long long)a.T * ((a.T + 31) & ~31) * 4 >= 0x7fffffffLL) return FS2HIP_EINVAL;  // one (utterance, head) slab per resource
-  const float dscale = a.drop.on ? a.drop.scale : 1.f;
-  attn2_prep_kernel<<<dim3((a.B * a.T + 3) / 4), dim3(256), 0, s>>>(dout, o, lse, reinterpret_cast<float2*>(aux), a.B, a.T,
-                                                                     a.H, a.HD, log2f(dscale), 1.f / dscale);
-  FS2_LAUNCH_CHECK();
-  dim3 grid(((a.T + 63) / 64) * a.H * a.B);
+  if (!fs2_attn_drop_index_ok(a) || fs2_attn2_bwd_spill_elems(a) == 0) return FS2HIP_EINVAL;
+  if (!fs2_attn_slab_ok(a.T, sizeof(float))) return FS2HIP_EINVAL;
+  if (const int rc = attn2_prep(a, o, dout, lse, aux, s)) return rc;
   const float2* ax = reinterpret_cast<const float2*>(aux);
-#define FS2_ATTN2_SPILL(HD_, DROP_)                                                                              \
-  if (s_in) attn2_bwd_dkv_kernel<HD_, DROP_, 0, true, true><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv, ds, s_in); \
-  else attn2_bwd_dkv_kernel<HD_, DROP_, 0, true><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv, ds);                  \
-  FS2_LAUNCH_CHECK();                                                                                            \
-  attn2_bwd_dq_ds_kernel<HD_><<<grid, dim3(256), 0, s>>>(a, ds, dqkv);
-  if (a.HD == 128) {
-    if (a.drop.on) { FS2_ATTN2_SPILL(128, true) } else { FS2_ATTN2_SPILL(128, false) }
-  } else {
-    if (a.drop.on) { FS2_ATTN2_SPILL(64, true) } else { FS2_ATTN2_SPILL(64, false) }
-  }
-#undef FS2_ATTN2_SPILL
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return attn2_pick(a, [&](auto hd, auto drop) {
+    return fs2_pick_bool(s_in != nullptr, [&](auto kept) {  // the scores the forward pass kept, instead of K.Q^T again
+      attn2_bwd_dkv_kernel<hd, drop, 0, true, kept><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, dout, ax, dqkv, ds, s_in);
+      FS2_LAUNCH_CHECK();
+      attn2_bwd_dq_ds_kernel<hd><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, ds, dqkv);
+      return fs2_launched();
+    });
+  });
 }
 
 #ifdef FS2_ATTN_STAMPS
 // diagnostic build: one of the two gradient kernels alone (which = 0: dQ, 1: dK/dV), HD = 128, after a prep launch
 int fs2_attn2_bwd_one(const Attn2Args& a, const float* dout, const float* aux, float* dqkv, int which, hipStream_t s) {
-  dim3 grid(((a.T + 63) / 64) * a.H * a.B);
   const float2* ax = reinterpret_cast<const float2*>(aux);
-#define FS2_ONE(K_, DROP_, P3_)                                                               \
-  if (a.planes == 3) K_<128, DROP_, P3_><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv);         \
-  else if (a.planes == 1) K_<128, DROP_, 1><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv);      \
-  else K_<128, DROP_, 0><<<grid, dim3(256), 0, s>>>(a, dout, ax, dqkv);
-  if (which == 0) {
-    if (a.drop.on) { FS2_ONE(attn2_bwd_dq_kernel, true, 3) } else { FS2_ONE(attn2_bwd_dq_kernel, false, 3) }
-  } else {
-    if (a.drop.on) { FS2_ONE(attn2_bwd_dkv_kernel, true, 0) } else { FS2_ONE(attn2_bwd_dkv_kernel, false, 0) }
-  }
-#undef FS2_ONE
-  return 0;
+  return fs2_pick_bool(a.drop.on, [&](auto drop) {
+    return attn2_pick_planes(a.planes, [&](auto planes) {
+      if (which == 0) attn2_bwd_dq_kernel<128, drop, planes><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, dout, ax, dqkv);
+      else attn2_bwd_dkv_kernel<128, drop, attn2_dkv_planes(planes)><<<fs2_attn_grid(a), dim3(256), 0, s>>>(a, dout, ax, dqkv);
+      return 0;
+    });
+  });
 }
 #endif

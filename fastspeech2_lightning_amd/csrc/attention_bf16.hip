@@ -22,6 +22,7 @@
 // The keep mask of the probabilities' dropout is attention2.hip's, bit for bit (attention_util.h).
 #include "attention2.h"
 #include "attention_util.h"
+#include "dispatch.h"
 #include "gemm_bf16_core.h"
 
 namespace {
@@ -673,23 +674,24 @@ __global__ __launch_bounds__(256, 1) void attnb_bwd_dkv_kernel(AttnBArgs p, cons
 
 bool fs2_attnb_supported(int HD) { return HD == AB_HD; }
 
+// what both launchers refuse: the shape, a dropout element index past 32 bits, an utterance's rows past one buffer range
+static bool attnb_shape_ok(const Attn2Args& a) {
+  if (a.HD != AB_HD || a.B <= 0 || a.T <= 0 || a.H <= 0 || !fs2_attn_drop_index_ok(a)) return false;
+  return (long long)a.T * 3 * a.H * a.HD * 2 < 0x7fffffffLL;
+}
+
 int fs2_attnb_fwd(const Attn2Args& a, const void* qkv, void* o, float* lse, hipStream_t s) {
-  if (a.HD != AB_HD || a.B <= 0 || a.T <= 0 || a.H <= 0) return FS2HIP_EINVAL;
-  if ((double)a.B * a.H * a.T * (a.T + (a.T & 1)) >= 4294967296.0) return FS2HIP_EINVAL;
-  if ((long long)a.T * 3 * a.H * a.HD * 2 >= 0x7fffffffLL) return FS2HIP_EINVAL;  // an utterance's rows within one buffer range
+  if (!attnb_shape_ok(a)) return FS2HIP_EINVAL;
   AttnBArgs p{(const u16*)qkv, a.lens, a.B, a.T, a.H, a.HD, a.scale, a.drop};
-  dim3 grid(((a.T + 127) / 128) * a.H * a.B);
-  if (a.drop.on) attnb_fwd_kernel<true><<<grid, dim3(256), 0, s>>>(p, (u16*)o, lse);
-  else attnb_fwd_kernel<false><<<grid, dim3(256), 0, s>>>(p, (u16*)o, lse);
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return fs2_pick_bool(a.drop.on, [&](auto drop) {
+    attnb_fwd_kernel<drop><<<fs2_attn_grid(a, 128), dim3(256), 0, s>>>(p, (u16*)o, lse);
+    return fs2_launched();
+  });
 }
 
 int fs2_attnb_bwd(const Attn2Args& a, const void* qkv, const void* o, const void* dout, const float* lse, float* aux,
                   void* dqkv, hipStream_t s, void* ds) {
-  if (a.HD != AB_HD || a.B <= 0 || a.T <= 0 || a.H <= 0) return FS2HIP_EINVAL;
-  if ((double)a.B * a.H * a.T * (a.T + (a.T & 1)) >= 4294967296.0) return FS2HIP_EINVAL;
-  if ((long long)a.T * 3 * a.H * a.HD * 2 >= 0x7fffffffLL) return FS2HIP_EINVAL;
+  if (!attnb_shape_ok(a)) return FS2HIP_EINVAL;
   AttnBArgs p{(const u16*)qkv, a.lens, a.B, a.T, a.H, a.HD, a.scale, a.drop};
   const float dscale = a.drop.on ? a.drop.scale : 1.f;
   const long long groups = (long long)a.B * a.T * a.H;
@@ -697,28 +699,24 @@ int fs2_attnb_bwd(const Attn2Args& a, const void* qkv, const void* o, const void
                                                                                reinterpret_cast<float2*>(aux), a.B, a.T, a.H,
                                                                                log2f(dscale), 1.f / dscale);
   FS2_LAUNCH_CHECK();
-  dim3 grid(((a.T + 127) / 128) * a.H * a.B);
+  // ds: dS spilled by the dK/dV kernel, dQ as a product of its own (B * H * T * (T rounded up to 32) bf16)
+  if (ds && (!fs2_attn_slab_ok(a.T, sizeof(u16)) || ((uintptr_t)ds % 16))) return FS2HIP_EINVAL;
+  const dim3 grid = fs2_attn_grid(a, 128);
   const float2* ax = reinterpret_cast<const float2*>(aux);
-  if (ds) {  // dS spilled by the dK/dV kernel, dQ as a product of its own (ds: B * H * T * (T rounded up to 32) bf16)
-    if ((long long)a.T * ((a.T + 31) & ~31) * 2 >= 0x7fffffffLL || ((uintptr_t)ds % 16)) return FS2HIP_EINVAL;
-    if (a.drop.on) attnb_bwd_dkv_kernel<true, true><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv, (u16*)ds);
-    else attnb_bwd_dkv_kernel<false, true><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv, (u16*)ds);
-    FS2_LAUNCH_CHECK();
-    attnb_bwd_dq_ds_kernel<<<grid, dim3(256), 0, s>>>(p, (const u16*)ds, (u16*)dqkv);
-    FS2_LAUNCH_CHECK();
-    return 0;
-  }
-  if (a.drop.on) {
-    attnb_bwd_dq_kernel<true><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv);
-    FS2_LAUNCH_CHECK();
-    attnb_bwd_dkv_kernel<true><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv);
-  } else {
-    attnb_bwd_dq_kernel<false><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv);
-    FS2_LAUNCH_CHECK();
-    attnb_bwd_dkv_kernel<false><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv);
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return fs2_pick_bool(a.drop.on, [&](auto drop) {
+    return fs2_pick_bool(ds != nullptr, [&](auto spill) {
+      if constexpr (spill) {
+        attnb_bwd_dkv_kernel<drop, true><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv, (u16*)ds);
+        FS2_LAUNCH_CHECK();
+        attnb_bwd_dq_ds_kernel<<<grid, dim3(256), 0, s>>>(p, (const u16*)ds, (u16*)dqkv);
+      } else {
+        attnb_bwd_dq_kernel<drop><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv);
+        FS2_LAUNCH_CHECK();
+        attnb_bwd_dkv_kernel<drop><<<grid, dim3(256), 0, s>>>(p, (const u16*)dout, ax, (u16*)dqkv);
+      }
+      return fs2_launched();
+    });
+  });
 }
 
 // a required tensor of the bf16-storage entry points: there, and accessed in 16-byte pieces

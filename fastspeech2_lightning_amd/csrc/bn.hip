@@ -12,6 +12,7 @@
 //   backward   : reduce (sum dz, sum dz*xhat) -> finalize (dgamma, dbeta, means) -> apply
 // The statistics passes sweep whole rows (contiguous >= 1 KiB per wavefront instruction).
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -386,10 +387,10 @@ extern "C" int fs2hip_colstats_b(const void* y, int M, int C, float* partial, in
   WideMap wm;
   if (M <= 0 || C <= 0 || !wide_ok(C, wm) || ((uintptr_t)y % (in_bf16 ? 8 : 16)) || ((uintptr_t)partial % 16)) return FS2HIP_EINVAL;
   const dim3 grid(fs2hip_colstats_parts(M));
-  if (in_bf16) colstats_wide_kernel<true><<<grid, dim3(256), 0, (hipStream_t)stream>>>(y, M, C, partial, wm);
-  else colstats_wide_kernel<false><<<grid, dim3(256), 0, (hipStream_t)stream>>>(y, M, C, partial, wm);
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return fs2_pick_bool(in_bf16 != 0, [&](auto ib) {
+    colstats_wide_kernel<ib><<<grid, dim3(256), 0, (hipStream_t)stream>>>(y, M, C, partial, wm);
+    return fs2_launched();
+  });
 }
 
 extern "C" int fs2hip_bn_finalize(const float* partial, int nparts, long long count, int part_rows, int group_rows,
@@ -428,12 +429,10 @@ extern "C" int fs2hip_bn_act_fwd_b(const void* y, const float* stats, float* out
   long long blocks = (n4 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
-  if (in_bf16)
-    bn_act_fwd_kernel<true><<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(y, stats, out, out_bf16, n4, C, act, drop);
-  else
-    bn_act_fwd_kernel<false><<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(y, stats, out, out_bf16, n4, C, act, drop);
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return fs2_pick_bool(in_bf16 != 0, [&](auto ib) {
+    bn_act_fwd_kernel<ib><<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(y, stats, out, out_bf16, n4, C, act, drop);
+    return fs2_launched();
+  });
 }
 
 // partial: [fs2hip_colstats_parts(M)][2][C]; coef: [2][C] scratch (16-byte aligned)
@@ -469,28 +468,18 @@ extern "C" int fs2hip_bn_act_bwd_b(const void* dout, const void* y, const float*
     return 0;
   }
   const int nparts = fs2hip_colstats_parts(M);
-#define FS2_BN_RED(IB_, DB_) bn_bwd_reduce_kernel<IB_, DB_><<<dim3(nparts), dim3(256), 0, s>>>(dout, y, stats, M, C, act, drop, partial, wm)
-  switch (in_bf16 & 3) {
-    case 0: FS2_BN_RED(false, false); break;
-    case 1: FS2_BN_RED(true, false); break;
-    case 2: FS2_BN_RED(false, true); break;
-    default: FS2_BN_RED(true, true); break;
-  }
-#undef FS2_BN_RED
-  FS2_LAUNCH_CHECK();
-  bn_bwd_finalize_kernel<<<dim3((C + FIN_CH - 1) / FIN_CH), dim3(1024), 0, s>>>(partial, nparts, (long long)M, dgamma, dbeta, coef, C);
-  FS2_LAUNCH_CHECK();
-  const long long n4 = (long long)M * C / 4;
-  long long blocks = (n4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-#define FS2_BN_APP(IB_, DB_) bn_bwd_apply_kernel<IB_, DB_><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(dout, y, stats, coef, dy, dy_bf16, n4, C, act, drop, training)
-  switch (in_bf16 & 3) {
-    case 0: FS2_BN_APP(false, false); break;
-    case 1: FS2_BN_APP(true, false); break;
-    case 2: FS2_BN_APP(false, true); break;
-    default: FS2_BN_APP(true, true); break;
-  }
-#undef FS2_BN_APP
-  FS2_LAUNCH_CHECK();
-  return 0;
+  // IB: y is bf16; DB: dout is
+  return fs2_pick_bool(in_bf16 & 1, [&](auto ib) {
+    return fs2_pick_bool(in_bf16 & 2, [&](auto db) {
+      bn_bwd_reduce_kernel<ib, db><<<dim3(nparts), dim3(256), 0, s>>>(dout, y, stats, M, C, act, drop, partial, wm);
+      FS2_LAUNCH_CHECK();
+      bn_bwd_finalize_kernel<<<dim3((C + FIN_CH - 1) / FIN_CH), dim3(1024), 0, s>>>(partial, nparts, (long long)M, dgamma, dbeta, coef, C);
+      FS2_LAUNCH_CHECK();
+      const long long n4 = (long long)M * C / 4;
+      long long blocks = (n4 + 255) / 256;
+      if (blocks > 8192) blocks = 8192;
+      bn_bwd_apply_kernel<ib, db><<<dim3((unsigned)blocks), dim3(256), 0, s>>>(dout, y, stats, coef, dy, dy_bf16, n4, C, act, drop, training);
+      return fs2_launched();
+    });
+  });
 }

@@ -5,6 +5,7 @@
 // DepthwiseSeparableConv1d (fs2/blocks.py:8-13).  HBM-bound: each input element is read once
 // (+ halo from L2), lanes run along channels so every row access is a contiguous 256-byte line.
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -805,29 +806,128 @@ __global__ __launch_bounds__(256) void dwconv_glu_bwd_tile_generic_kernel(const 
   }
 }
 
-bool dw_force_generic() {  // FS2_DWCONV_GENERIC=1: every width on the run-time-K kernels (measurement and test aid)
-  const char* e = getenv("FS2_DWCONV_GENERIC");
-  return e && atoi(e) != 0;
+bool dw_env_flag(const char* name, int value) {  // read at every call: tests and measurements flip them inside a process
+  const char* e = getenv(name);
+  return e && (atoi(e) != 0) == (value != 0);
 }
+bool dw_force_generic() { return dw_env_flag("FS2_DWCONV_GENERIC", 1); }  // every width on the run-time-K kernels
+bool dw_tiles_off() { return dw_env_flag("FS2_DWCONV_TILE", 0); }  // the per-thread-window kernels everywhere
 bool dw_generic_width(int K) { return K >= 1 && K <= KMAX && (K & 1); }
+
+// The forms there are kernels for; the entry points refuse the others, the launchers instantiate nothing for them.
+// Forward, io 0: fp32 tensors; 1: bf16 tensors -- the Conformer convolution module's GLU form only; 2: fp32 in, bf16 out
+// -- the variance predictors' plain depthwise layer feeding a bf16-storage GEMM, without statistics.
+constexpr bool dw_fwd_form(bool glu, bool stats, int io) {
+  return io == 0 || (io == 1 && glu) || (io == 2 && !glu && !stats);
+}
+// Backward, x_bf16: dy and x are bf16 tensors -- the GLU form with a bf16 result only.
+constexpr bool dw_bwd_form(bool glu, bool dx_bf16, bool x_bf16) { return !x_bf16 || (glu && dx_bf16); }
+
+// The width as a constant for the six instantiated ones; 0: any other width, or FS2_DWCONV_GENERIC=1 -- the run-time-K
+// kernels, which take K as their last argument and stage their windows in dynamic LDS.
+template <class F>
+int dw_pick_width(int K, F&& f) {
+  return fs2_pick_int<0, 3, 5, 7, 9, 15, 31>(dw_force_generic() ? 0 : K, f);
+}
+size_t dw_fwd_shm(int K) { return (size_t)(dwg_rows(K) * 64 + 4 * 2 * 64) * sizeof(float); }
+size_t dw_bwd_shm(int K) { return (size_t)(2 * dwg_rows(K) * 64) * sizeof(float); }
+
+struct DwLaunch {
+  dim3 grid;
+  hipStream_t s;
+  int B, T, C, K;
+};
+DwLaunch dw_launch(int B, int T, int C, int K, void* stream) {
+  return {dim3((C + 63) / 64, (T + 4 * RUN - 1) / (4 * RUN), B), (hipStream_t)stream, B, T, C, K};
+}
+
+int dw_fwd_plain(const DwLaunch& l, const void* x, int ldx, const float* w, const float* bias, void* y, float* partial,
+                 bool glu, bool stats, int io) {
+  return dw_pick_width(l.K, [&](auto kc) {
+    return fs2_pick_bool(glu, [&](auto g) {
+      return fs2_pick_bool(stats, [&](auto st) {
+        return fs2_pick_int<0, 1, 2>(io, [&](auto ioc) {
+          constexpr bool XB = ioc == 1, YB = ioc != 0;
+          if constexpr (!dw_fwd_form(g, st, ioc)) {
+            return (int)FS2HIP_EINVAL;
+          } else if constexpr (kc == 0) {
+            if (!dw_generic_width(l.K)) return (int)FS2HIP_EINVAL;
+            dwconv_fwd_generic_kernel<g, st, XB, YB><<<l.grid, dim3(256), dw_fwd_shm(l.K), l.s>>>(x, ldx, w, bias, y, partial,
+                                                                                                 l.B, l.T, l.C, l.K);
+            return fs2_launched();
+          } else {
+            dwconv_fwd_kernel<kc, g, st, XB, YB><<<l.grid, dim3(256), 0, l.s>>>(x, ldx, w, bias, y, partial, l.B, l.T, l.C);
+            return fs2_launched();
+          }
+        });
+      });
+    });
+  });
+}
+
+// the LDS-tiled GLU kernels: x_bf16 = x and y are bf16 tensors
+int dw_fwd_tile(const DwLaunch& l, const void* x, int ldx, const float* w, const float* bias, void* y, float* partial,
+                bool stats, bool x_bf16) {
+  return dw_pick_width(l.K, [&](auto kc) {
+    return fs2_pick_bool(stats, [&](auto st) {
+      return fs2_pick_bool(x_bf16, [&](auto xb) {
+        if constexpr (kc == 0) {
+          if (!dw_generic_width(l.K)) return (int)FS2HIP_EINVAL;
+          dwconv_glu_fwd_tile_generic_kernel<st, xb><<<l.grid, dim3(256), dw_fwd_shm(l.K), l.s>>>(x, ldx, w, bias, y, partial,
+                                                                                                 l.B, l.T, l.C, l.K);
+        } else {
+          dwconv_glu_fwd_tile_kernel<kc, st, xb><<<l.grid, dim3(256), 0, l.s>>>(x, ldx, w, bias, y, partial, l.B, l.T, l.C);
+        }
+        return fs2_launched();
+      });
+    });
+  });
+}
+
+int dw_bwd_plain(const DwLaunch& l, const void* dy, const void* x, int ldx, const float* w, void* dx, float* partial,
+                 bool glu, bool dx_bf16, bool x_bf16) {
+  return dw_pick_width(l.K, [&](auto kc) {
+    return fs2_pick_bool(glu, [&](auto g) {
+      return fs2_pick_bool(dx_bf16, [&](auto dxb) {
+        return fs2_pick_bool(x_bf16, [&](auto xb) {
+          if constexpr (!dw_bwd_form(g, dxb, xb)) {
+            return (int)FS2HIP_EINVAL;
+          } else if constexpr (kc == 0) {
+            if (!dw_generic_width(l.K)) return (int)FS2HIP_EINVAL;
+            dwconv_bwd_generic_kernel<g, dxb, xb><<<l.grid, dim3(256), dw_bwd_shm(l.K), l.s>>>(dy, x, ldx, w, dx, partial, l.B,
+                                                                                              l.T, l.C, l.K);
+            return fs2_launched();
+          } else {
+            dwconv_bwd_kernel<kc, g, dxb, xb><<<l.grid, dim3(256), 0, l.s>>>(dy, x, ldx, w, dx, partial, l.B, l.T, l.C);
+            return fs2_launched();
+          }
+        });
+      });
+    });
+  });
+}
+
+// the LDS-tiled GLU kernels: the type of dx is a run-time argument of theirs
+int dw_bwd_tile(const DwLaunch& l, const void* dy, const void* x, int ldx, const float* w, void* dx, float* partial,
+                int dx_bf16, bool x_bf16) {
+  return dw_pick_width(l.K, [&](auto kc) {
+    return fs2_pick_bool(x_bf16, [&](auto xb) {
+      if constexpr (kc == 0) {
+        if (!dw_generic_width(l.K)) return (int)FS2HIP_EINVAL;
+        dwconv_glu_bwd_tile_generic_kernel<xb><<<l.grid, dim3(256), dw_bwd_shm(l.K), l.s>>>(dy, x, ldx, w, dx, partial, l.B,
+                                                                                           l.T, l.C, dx_bf16, l.K);
+      } else {
+        dwconv_glu_bwd_tile_kernel<kc, xb><<<l.grid, dim3(256), 0, l.s>>>(dy, x, ldx, w, dx, partial, l.B, l.T, l.C, dx_bf16);
+      }
+      return fs2_launched();
+    });
+  });
+}
 
 }  // namespace
 
 extern "C" int fs2hip_dwconv_blocks(int B, int T) { return B * ((T + 4 * RUN - 1) / (4 * RUN)); }
 extern "C" int fs2hip_dwconv_part_rows(void) { return 4 * RUN; }
-
-#define DW_FWD(KK)                                                                                              \
-  if (io_bf16 == 2) { /* fp32 in, bf16 out: the variance predictors' plain depthwise layer feeding a bf16-storage GEMM */ \
-    if (glu || stats) return FS2HIP_EINVAL;                                                                     \
-    dwconv_fwd_kernel<KK, false, false, false, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C); \
-  } else if (io_bf16) {                                                                                         \
-    if (!glu) return FS2HIP_EINVAL; /* bf16 tensors: the Conformer convolution module's GLU form only */         \
-    if (stats) dwconv_fwd_kernel<KK, true, true, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C); \
-    else dwconv_fwd_kernel<KK, true, false, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);      \
-  } else if (glu && stats) dwconv_fwd_kernel<KK, true, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C); \
-  else if (glu) dwconv_fwd_kernel<KK, true, false><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);   \
-  else if (stats) dwconv_fwd_kernel<KK, false, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C); \
-  else dwconv_fwd_kernel<KK, false, false><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);
 
 extern "C" int fs2hip_dwconv_fwd_b(const void* x, int ldx, const float* w, const float* bias, void* y, float* partial,
                                    int B, int T, int C, int K, int glu, int stats, int io_bf16, void* stream);
@@ -841,73 +941,12 @@ extern "C" int fs2hip_dwconv_fwd_b(const void* x, int ldx, const float* w, const
                                    int B, int T, int C, int K, int glu, int stats, int io_bf16, void* stream) {
   if (B <= 0 || T <= 0 || C <= 0 || ldx < (glu ? 2 * C : C)) return FS2HIP_EINVAL;
   if (stats && !partial) return FS2HIP_EINVAL;
-  dim3 grid((C + 63) / 64, (T + 4 * RUN - 1) / (4 * RUN), B);
-  hipStream_t s = (hipStream_t)stream;
-  const char* tile_env = getenv("FS2_DWCONV_TILE");  // "0": the per-thread-window kernels everywhere (measurement aid, tests)
-  const bool tiles_off = tile_env && atoi(tile_env) == 0;
-  if (io_bf16 != 0 && io_bf16 != 1 && io_bf16 != 2) return FS2HIP_EINVAL;
-  if (io_bf16 == 2 && (glu || stats)) return FS2HIP_EINVAL;
-  const int kk = dw_force_generic() ? 0 : K;  // 0: no instantiated width, i.e. the run-time-K kernels
-  const size_t shm = (size_t)(dwg_rows(K) * 64 + 4 * 2 * 64) * sizeof(float);
-  if (glu && !tiles_off && (C % 64) == 0 && (ldx % 8) == 0 && ((uintptr_t)x % 16) == 0) {
-#define DW_FWD_T(KK)                                                                                              \
-  if (io_bf16 && stats) dwconv_glu_fwd_tile_kernel<KK, true, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);        \
-  else if (io_bf16) dwconv_glu_fwd_tile_kernel<KK, false, true><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);          \
-  else if (stats) dwconv_glu_fwd_tile_kernel<KK, true, false><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);            \
-  else dwconv_glu_fwd_tile_kernel<KK, false, false><<<grid, dim3(256), 0, s>>>(x, ldx, w, bias, y, partial, B, T, C);
-    switch (kk) {
-      case 3: DW_FWD_T(3) break;
-      case 5: DW_FWD_T(5) break;
-      case 7: DW_FWD_T(7) break;
-      case 9: DW_FWD_T(9) break;
-      case 15: DW_FWD_T(15) break;
-      case 31: DW_FWD_T(31) break;
-      default:
-        if (!dw_generic_width(K)) return FS2HIP_EINVAL;
-        if (io_bf16 && stats) dwconv_glu_fwd_tile_generic_kernel<true, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-        else if (io_bf16) dwconv_glu_fwd_tile_generic_kernel<false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-        else if (stats) dwconv_glu_fwd_tile_generic_kernel<true, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-        else dwconv_glu_fwd_tile_generic_kernel<false, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-    }
-#undef DW_FWD_T
-    FS2_LAUNCH_CHECK();
-    return 0;
-  }
-  switch (kk) {
-    case 3: DW_FWD(3) break;
-    case 5: DW_FWD(5) break;
-    case 7: DW_FWD(7) break;
-    case 9: DW_FWD(9) break;
-    case 15: DW_FWD(15) break;
-    case 31: DW_FWD(31) break;
-    default:
-      if (!dw_generic_width(K)) return FS2HIP_EINVAL;
-      if (io_bf16 == 2) {
-        dwconv_fwd_generic_kernel<false, false, false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-      } else if (io_bf16) {
-        if (!glu) return FS2HIP_EINVAL;
-        if (stats) dwconv_fwd_generic_kernel<true, true, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-        else dwconv_fwd_generic_kernel<true, false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-      } else if (glu && stats) dwconv_fwd_generic_kernel<true, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-      else if (glu) dwconv_fwd_generic_kernel<true, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-      else if (stats) dwconv_fwd_generic_kernel<false, true><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-      else dwconv_fwd_generic_kernel<false, false><<<grid, dim3(256), shm, s>>>(x, ldx, w, bias, y, partial, B, T, C, K);
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
+  if (io_bf16 < 0 || io_bf16 > 2 || !dw_fwd_form(glu, stats, io_bf16)) return FS2HIP_EINVAL;
+  const DwLaunch l = dw_launch(B, T, C, K, stream);
+  if (glu && !dw_tiles_off() && (C % 64) == 0 && (ldx % 8) == 0 && ((uintptr_t)x % 16) == 0)
+    return dw_fwd_tile(l, x, ldx, w, bias, y, partial, stats, io_bf16 == 1);
+  return dw_fwd_plain(l, x, ldx, w, bias, y, partial, glu, stats, io_bf16);
 }
-
-#define DW_BWD(KK)                                                                                                \
-  if (dx_bf16 & 2) {                                                                                              \
-    if (!glu || !(dx_bf16 & 1)) return FS2HIP_EINVAL; /* bf16 inputs: GLU form with a bf16 result only */          \
-    dwconv_bwd_kernel<KK, true, true, true><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C);       \
-  } else if (dx_bf16) {                                                                                           \
-    if (glu) dwconv_bwd_kernel<KK, true, true><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C);    \
-    else dwconv_bwd_kernel<KK, false, true><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C);       \
-  } else {                                                                                                        \
-    if (glu) dwconv_bwd_kernel<KK, true><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C);          \
-    else dwconv_bwd_kernel<KK, false><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C);             \
-  }
 
 // partial: [fs2hip_dwconv_blocks(B,T)][K+1][C]; dw [K][C], dbias [C] are finished here
 extern "C" int fs2hip_dwconv_bwd_b(const void* dy, const void* x, int ldx, const float* w, void* dx, int dx_bf16,
@@ -923,53 +962,14 @@ extern "C" int fs2hip_dwconv_bwd_b(const void* dy, const void* x, int ldx, const
                                    float* partial, float* dw, float* dbias, int B, int T, int C, int K, int glu,
                                    void* stream) {
   if (B <= 0 || T <= 0 || C <= 0 || ldx < (glu ? 2 * C : C) || !partial) return FS2HIP_EINVAL;
-  dim3 grid((C + 63) / 64, (T + 4 * RUN - 1) / (4 * RUN), B);
-  hipStream_t s = (hipStream_t)stream;
-  const char* tile_env = getenv("FS2_DWCONV_TILE");  // "0": the per-thread-window kernels everywhere (measurement aid, tests)
-  const bool tiles_off = tile_env && atoi(tile_env) == 0;
-  const int kk = dw_force_generic() ? 0 : K;  // 0: no instantiated width, i.e. the run-time-K kernels
-  const size_t shm = (size_t)(2 * dwg_rows(K) * 64) * sizeof(float);
-  if (glu && !tiles_off && (C % 64) == 0 && (ldx % 8) == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)dy % 16) == 0) {
-    if ((dx_bf16 & 2) && !(dx_bf16 & 1)) return FS2HIP_EINVAL;
-#define DW_BWD_T(KK)                                                                                              \
-  if (dx_bf16 & 2) dwconv_glu_bwd_tile_kernel<KK, true><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C, 1); \
-  else dwconv_glu_bwd_tile_kernel<KK, false><<<grid, dim3(256), 0, s>>>(dy, x, ldx, w, dx, partial, B, T, C, dx_bf16 & 1);
-    switch (kk) {
-      case 3: DW_BWD_T(3) break;
-      case 5: DW_BWD_T(5) break;
-      case 7: DW_BWD_T(7) break;
-      case 9: DW_BWD_T(9) break;
-      case 15: DW_BWD_T(15) break;
-      case 31: DW_BWD_T(31) break;
-      default:
-        if (!dw_generic_width(K)) return FS2HIP_EINVAL;
-        if (dx_bf16 & 2) dwconv_glu_bwd_tile_generic_kernel<true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, 1, K);
-        else dwconv_glu_bwd_tile_generic_kernel<false><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, dx_bf16 & 1, K);
-    }
-#undef DW_BWD_T
-  } else {
-    switch (kk) {
-      case 3: DW_BWD(3) break;
-      case 5: DW_BWD(5) break;
-      case 7: DW_BWD(7) break;
-      case 9: DW_BWD(9) break;
-      case 15: DW_BWD(15) break;
-      case 31: DW_BWD(31) break;
-      default:
-        if (!dw_generic_width(K)) return FS2HIP_EINVAL;
-        if (dx_bf16 & 2) {
-          if (!glu || !(dx_bf16 & 1)) return FS2HIP_EINVAL;
-          dwconv_bwd_generic_kernel<true, true, true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
-        } else if (dx_bf16) {
-          if (glu) dwconv_bwd_generic_kernel<true, true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
-          else dwconv_bwd_generic_kernel<false, true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
-        } else {
-          if (glu) dwconv_bwd_generic_kernel<true><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
-          else dwconv_bwd_generic_kernel<false><<<grid, dim3(256), shm, s>>>(dy, x, ldx, w, dx, partial, B, T, C, K);
-        }
-    }
-  }
-  FS2_LAUNCH_CHECK();
+  const bool x_bf16 = dx_bf16 & 2;
+  if (!dw_bwd_form(glu, dx_bf16 & 1, x_bf16)) return FS2HIP_EINVAL;
+  const DwLaunch l = dw_launch(B, T, C, K, stream);
+  const bool tile = glu && !dw_tiles_off() && (C % 64) == 0 && (ldx % 8) == 0 && ((uintptr_t)x % 16) == 0 &&
+                    ((uintptr_t)dy % 16) == 0;
+  const int launched = tile ? dw_bwd_tile(l, dy, x, ldx, w, dx, partial, dx_bf16 & 1, x_bf16)
+                            : dw_bwd_plain(l, dy, x, ldx, w, dx, partial, glu, dx_bf16 != 0, x_bf16);
+  if (launched) return launched;
   if (!dw) return 0;  // partial sums only: the caller finishes them with fs2hip_reduce_rows_multi (same sums, same order)
   const int nblk = fs2hip_dwconv_blocks(B, T);
   const long long stride = (long long)(K + 1) * C;

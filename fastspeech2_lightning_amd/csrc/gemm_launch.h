@@ -5,6 +5,7 @@
 #pragma once
 #include <type_traits>
 
+#include "dispatch.h"
 #include "gemm_common.h"
 #include "gemm_tiles.h"
 
@@ -22,12 +23,6 @@ inline int fs2_set_tiles(GemmP& p, int nz) {
   p.tiles_n = (p.a.Nc + BN - 1) / BN;
   const long long units = (long long)p.tiles_m * p.tiles_n * nz;
   return units > 0x7fffffffLL ? 0 : (int)units;
-}
-
-// what a launcher returns behind its <<<>>>: the launch error, if any
-inline int fs2_launched() {
-  FS2_LAUNCH_CHECK();
-  return 0;
 }
 
 // Number of CUs of the current device, asked once per process; 0 = the query failed (the caller refuses).

@@ -358,13 +358,8 @@ __global__ __launch_bounds__(WS_THREADS, (NB == 1 && OBF) ? 4 : 2) void gemmws_k
   ws_vmwait<0>();  // nothing of this wavefront may still be writing LDS or memory when the workgroup's LDS is released
 }
 
-#define WS_GO(NB_, EPI_, ACT_, OBF_, TWO_, AUXB_)                                                                       \
-  do {                                                                                                                  \
-    if ((EPI_) > 0 && p.drop.on)                                                                                        \
-      gemmws_kernel<NB_, EPI_, ACT_, OBF_, TWO_, AUXB_, ((EPI_) > 0)><<<grid, block, 0, s>>>(p, n_slices, n_streams, n_row_tiles); \
-    else                                                                                                                \
-      gemmws_kernel<NB_, EPI_, ACT_, OBF_, TWO_, AUXB_, false><<<grid, block, 0, s>>>(p, n_slices, n_streams, n_row_tiles);   \
-  } while (0)
+template <int V>
+using WsC = std::integral_constant<int, V>;
 
 template <int NB>
 int launch_ws(GemmP& p, hipStream_t s) {
@@ -385,36 +380,33 @@ int launch_ws(GemmP& p, hipStream_t s) {
                       (a.epi == FS2_EPI_DACT && obf && auxb && drop_on && a.act == FS2_ACT_SILU);
     if (!fits) return FS2HIP_EINVAL;
   }
+  // The instance of (epilogue, activation, second fp32 output, bf16 aux) x bf16 result x dropout.  act -1: the kernel
+  // reads a.act at run time.  (NB = 2 has every instance NB = 1 has, those `fits` never lets through included.)
+  auto go = [&](auto epi, auto act, auto two_c, auto auxb_c) {
+    return fs2_pick_bool(obf, [&](auto ob) {
+      return fs2_pick_bool(p.drop.on, [&](auto dr) {
+        gemmws_kernel<NB, epi, act, ob, two_c, auxb_c, (epi > 0 && dr)><<<grid, block, 0, s>>>(p, n_slices, n_streams, n_row_tiles);
+        return fs2_launched();
+      });
+    });
+  };
+  auto silu_or_any = [&](auto&& f) { return fs2_pick_int<-1, FS2_ACT_SILU>(a.act, f); };
+  constexpr std::false_type no{};
   switch (a.epi) {
     case FS2_EPI_ACT:
-      if (a.act == FS2_ACT_SILU) {
-        if (obf) { if (two) WS_GO(NB, FS2_EPI_ACT, FS2_ACT_SILU, true, true, false); else WS_GO(NB, FS2_EPI_ACT, FS2_ACT_SILU, true, false, false); }
-        else { if (two) WS_GO(NB, FS2_EPI_ACT, FS2_ACT_SILU, false, true, false); else WS_GO(NB, FS2_EPI_ACT, FS2_ACT_SILU, false, false, false); }
-      } else {
-        if (obf) { if (two) WS_GO(NB, FS2_EPI_ACT, -1, true, true, false); else WS_GO(NB, FS2_EPI_ACT, -1, true, false, false); }
-        else { if (two) WS_GO(NB, FS2_EPI_ACT, -1, false, true, false); else WS_GO(NB, FS2_EPI_ACT, -1, false, false, false); }
-      }
-      break;
+      return silu_or_any([&](auto act) {
+        return fs2_pick_bool(two, [&](auto two_c) { return go(WsC<FS2_EPI_ACT>{}, act, two_c, no); });
+      });
     case FS2_EPI_RESID:
-      if (obf) WS_GO(NB, FS2_EPI_RESID, -1, true, false, false); else WS_GO(NB, FS2_EPI_RESID, -1, false, false, false);
-      break;
+      return go(WsC<FS2_EPI_RESID>{}, WsC<-1>{}, no, no);
     case FS2_EPI_DACT:
-      if (a.act == FS2_ACT_SILU) {
-        if (obf) { if (auxb) WS_GO(NB, FS2_EPI_DACT, FS2_ACT_SILU, true, false, true); else WS_GO(NB, FS2_EPI_DACT, FS2_ACT_SILU, true, false, false); }
-        else { if (auxb) WS_GO(NB, FS2_EPI_DACT, FS2_ACT_SILU, false, false, true); else WS_GO(NB, FS2_EPI_DACT, FS2_ACT_SILU, false, false, false); }
-      } else {
-        if (obf) { if (auxb) WS_GO(NB, FS2_EPI_DACT, -1, true, false, true); else WS_GO(NB, FS2_EPI_DACT, -1, true, false, false); }
-        else { if (auxb) WS_GO(NB, FS2_EPI_DACT, -1, false, false, true); else WS_GO(NB, FS2_EPI_DACT, -1, false, false, false); }
-      }
-      break;
+      return silu_or_any([&](auto act) {
+        return fs2_pick_bool(auxb, [&](auto auxb_c) { return go(WsC<FS2_EPI_DACT>{}, act, no, auxb_c); });
+      });
     default:
-      if (obf) WS_GO(NB, 0, -1, true, false, false); else WS_GO(NB, 0, -1, false, false, false);
-      break;
+      return go(WsC<FS2_EPI_STORE>{}, WsC<-1>{}, no, no);
   }
-  FS2_LAUNCH_CHECK();
-  return 0;
 }
-#undef WS_GO
 
 }  // namespace
 

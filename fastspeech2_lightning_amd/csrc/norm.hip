@@ -3,6 +3,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "dispatch.h"
 
 namespace {
 
@@ -211,132 +212,100 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
   }
 }
 
+// NCH of a launch: the float4 chunks per lane that cover C channels -- 1, 2, or (three included) the 4-chunk instance
+template <class F>
+int ln_pick_nch(int C, F&& f) {
+  return fs2_pick_int<4, 1, 2>((C / 4 + 63) / 64, f);
+}
+
+template <bool YB, bool DROP>
+int ln_fwd_launch(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int M, int C,
+                  float eps, Fs2Drop drop, void* stream) {
+  return ln_pick_nch(C, [&](auto nch) {
+    ln_fwd_kernel<nch, YB, DROP><<<dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(x, gamma, beta, y, mean, rstd, M,
+                                                                                          C, eps, drop);
+    return fs2_launched();
+  });
+}
+
+template <bool DZ, bool DYB, bool ZB, bool PRED, bool XOB>
+int ln_bwd_launch(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                  const float* dx_add, void* dx, float* partial, int M, int C, void* dz, float dz_scale, Fs2Drop drop,
+                  void* stream) {
+  return ln_pick_nch(C, [&](auto nch) {
+    ln_bwd_kernel<nch, DZ, DYB, ZB, PRED, XOB><<<dim3(fs2hip_layernorm_bwd_blocks(M)), dim3(256), 0, (hipStream_t)stream>>>(
+        dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale, drop, ln_bwd_rows(M));
+    return fs2_launched();
+  });
+}
+
+// what every entry point refuses: the shape, and tensors the float4 accesses cannot take
+bool ln_shape_ok(int M, int C) { return M > 0 && C > 0 && (C % 4) == 0 && C <= LN_MAX_CH * 256; }
+bool ln_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
 }  // namespace
-
-extern "C" int fs2hip_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y,
-                                    float* mean, float* rstd, int M, int C, float eps, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256) return FS2HIP_EINVAL;
-  if (((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16)) return FS2HIP_EINVAL;
-  dim3 grid((M + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const int nch = (C / 4 + 63) / 64;
-  switch (nch) {
-    case 1: ln_fwd_kernel<1, false><<<grid, block, 0, s>>>(x, gamma, beta, y, mean, rstd, M, C, eps); break;
-    case 2: ln_fwd_kernel<2, false><<<grid, block, 0, s>>>(x, gamma, beta, y, mean, rstd, M, C, eps); break;
-    default: ln_fwd_kernel<4, false><<<grid, block, 0, s>>>(x, gamma, beta, y, mean, rstd, M, C, eps); break;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int fs2hip_layernorm_fwd_drop(const float* x, const float* gamma, const float* beta, float* y, float* mean,
-                                         float* rstd, int M, int C, float eps, float drop_p, unsigned long long drop_seed,
-                                         const unsigned long long* drop_step, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256 || (long long)M * C >= 0x7fffffffLL) return FS2HIP_EINVAL;
-  if (((uintptr_t)x % 16) || ((uintptr_t)y % 16) || ((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16)) return FS2HIP_EINVAL;
-  if (!(drop_p > 0.f)) return fs2hip_layernorm_fwd(x, gamma, beta, y, mean, rstd, M, C, eps, stream);
-  dim3 grid((M + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
-  const int nch = (C / 4 + 63) / 64;
-  switch (nch) {
-    case 1: ln_fwd_kernel<1, false, true><<<grid, block, 0, s>>>(x, gamma, beta, y, mean, rstd, M, C, eps, drop); break;
-    case 2: ln_fwd_kernel<2, false, true><<<grid, block, 0, s>>>(x, gamma, beta, y, mean, rstd, M, C, eps, drop); break;
-    default: ln_fwd_kernel<4, false, true><<<grid, block, 0, s>>>(x, gamma, beta, y, mean, rstd, M, C, eps, drop); break;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int fs2hip_layernorm_bwd_pred(const float* dy, const float* x, const float* gamma, const float* mean,
-                                         const float* rstd, void* dx, int dx_bf16, float* partial, int M, int C, float drop_p,
-                                         unsigned long long drop_seed, const unsigned long long* drop_step, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256 || !partial || (long long)M * C >= 0x7fffffffLL) return FS2HIP_EINVAL;
-  if (((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)gamma % 16)) return FS2HIP_EINVAL;
-  const int nblk = fs2hip_layernorm_bwd_blocks(M);
-  hipStream_t s = (hipStream_t)stream;
-  const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);  // (p = 0: every factor is 1)
-  const int nch = (C / 4 + 63) / 64;
-#define LN_PRED(N_, XOB_) ln_bwd_kernel<N_, false, false, false, true, XOB_><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, nullptr, dx, partial, M, C, nullptr, 0.f, drop, ln_bwd_rows(M))
-  if (dx_bf16) {
-    switch (nch) {
-      case 1: LN_PRED(1, true); break;
-      case 2: LN_PRED(2, true); break;
-      default: LN_PRED(4, true); break;
-    }
-  } else {
-    switch (nch) {
-      case 1: LN_PRED(1, false); break;
-      case 2: LN_PRED(2, false); break;
-      default: LN_PRED(4, false); break;
-    }
-  }
-#undef LN_PRED
-  FS2_LAUNCH_CHECK();
-  return 0;  // partial is [nblk][2][C]: dgamma | dbeta partial sums, finished by fs2hip_reduce_rows_multi
-}
-
-extern "C" int fs2hip_layernorm_fwd_b(const float* x, const float* gamma, const float* beta, void* y_bf16,
-                                      float* mean, float* rstd, int M, int C, float eps, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256) return FS2HIP_EINVAL;
-  if (((uintptr_t)x % 16) || ((uintptr_t)y_bf16 % 8) || ((uintptr_t)gamma % 16) || ((uintptr_t)beta % 16)) return FS2HIP_EINVAL;
-  dim3 grid((M + 3) / 4), block(256);
-  hipStream_t s = (hipStream_t)stream;
-  const int nch = (C / 4 + 63) / 64;
-  switch (nch) {
-    case 1: ln_fwd_kernel<1, true><<<grid, block, 0, s>>>(x, gamma, beta, y_bf16, mean, rstd, M, C, eps); break;
-    case 2: ln_fwd_kernel<2, true><<<grid, block, 0, s>>>(x, gamma, beta, y_bf16, mean, rstd, M, C, eps); break;
-    default: ln_fwd_kernel<4, true><<<grid, block, 0, s>>>(x, gamma, beta, y_bf16, mean, rstd, M, C, eps); break;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;
-}
 
 extern "C" int fs2hip_layernorm_bwd_blocks(int M) {
   const int rows = ln_bwd_rows(M);
   return (M + rows - 1) / rows;
 }
 
+extern "C" int fs2hip_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y,
+                                    float* mean, float* rstd, int M, int C, float eps, void* stream) {
+  if (!ln_shape_ok(M, C) || !ln_al16(x) || !ln_al16(y) || !ln_al16(gamma) || !ln_al16(beta)) return FS2HIP_EINVAL;
+  return ln_fwd_launch<false, false>(x, gamma, beta, y, mean, rstd, M, C, eps, Fs2Drop{}, stream);
+}
+
+extern "C" int fs2hip_layernorm_fwd_drop(const float* x, const float* gamma, const float* beta, float* y, float* mean,
+                                         float* rstd, int M, int C, float eps, float drop_p, unsigned long long drop_seed,
+                                         const unsigned long long* drop_step, void* stream) {
+  if (!ln_shape_ok(M, C) || (long long)M * C >= 0x7fffffffLL) return FS2HIP_EINVAL;
+  if (!ln_al16(x) || !ln_al16(y) || !ln_al16(gamma) || !ln_al16(beta)) return FS2HIP_EINVAL;
+  if (!(drop_p > 0.f)) return fs2hip_layernorm_fwd(x, gamma, beta, y, mean, rstd, M, C, eps, stream);
+  return ln_fwd_launch<false, true>(x, gamma, beta, y, mean, rstd, M, C, eps, fs2_make_drop(drop_p, drop_seed, drop_step),
+                                    stream);
+}
+
+extern "C" int fs2hip_layernorm_fwd_b(const float* x, const float* gamma, const float* beta, void* y_bf16,
+                                      float* mean, float* rstd, int M, int C, float eps, void* stream) {
+  if (!ln_shape_ok(M, C) || !ln_al16(x) || ((uintptr_t)y_bf16 % 8) || !ln_al16(gamma) || !ln_al16(beta)) return FS2HIP_EINVAL;
+  return ln_fwd_launch<true, false>(x, gamma, beta, y_bf16, mean, rstd, M, C, eps, Fs2Drop{}, stream);
+}
+
+// partial is [nblk][2][C]: dgamma | dbeta partial sums, finished by fs2hip_reduce_rows_multi
+extern "C" int fs2hip_layernorm_bwd_pred(const float* dy, const float* x, const float* gamma, const float* mean,
+                                         const float* rstd, void* dx, int dx_bf16, float* partial, int M, int C, float drop_p,
+                                         unsigned long long drop_seed, const unsigned long long* drop_step, void* stream) {
+  if (!ln_shape_ok(M, C) || !partial || (long long)M * C >= 0x7fffffffLL) return FS2HIP_EINVAL;
+  if (!ln_al16(x) || !ln_al16(dy) || !ln_al16(dx) || !ln_al16(gamma)) return FS2HIP_EINVAL;
+  const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);  // (p = 0: every factor is 1)
+  return fs2_pick_bool(dx_bf16 != 0, [&](auto xob) {
+    return ln_bwd_launch<false, false, false, true, xob>(dy, x, gamma, mean, rstd, nullptr, dx, partial, M, C, nullptr, 0.f,
+                                                         drop, stream);
+  });
+}
+
 extern "C" int fs2hip_layernorm_bwd(const float* dy, const float* x, const float* gamma, const float* mean,
                                     const float* rstd, const float* dx_add, float* dx, float* partial,
                                     float* dgamma, float* dbeta, int M, int C, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256 || !partial) return FS2HIP_EINVAL;
-  if (((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)gamma % 16)) return FS2HIP_EINVAL;
-  if (dx_add && ((uintptr_t)dx_add % 16)) return FS2HIP_EINVAL;
-  const int nblk = fs2hip_layernorm_bwd_blocks(M);
-  hipStream_t s = (hipStream_t)stream;
-  const int nch = (C / 4 + 63) / 64;
-  const Fs2Drop nodrop = fs2_make_drop(0.f, 0);
-  switch (nch) {
-    case 1: ln_bwd_kernel<1, false><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, nullptr, 0.f, nodrop, ln_bwd_rows(M)); break;
-    case 2: ln_bwd_kernel<2, false><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, nullptr, 0.f, nodrop, ln_bwd_rows(M)); break;
-    default: ln_bwd_kernel<4, false><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, nullptr, 0.f, nodrop, ln_bwd_rows(M)); break;
-  }
-  FS2_LAUNCH_CHECK();
+  if (!ln_shape_ok(M, C) || !partial) return FS2HIP_EINVAL;
+  if (!ln_al16(x) || !ln_al16(dy) || !ln_al16(dx) || !ln_al16(gamma) || !ln_al16(dx_add)) return FS2HIP_EINVAL;
+  const int rc = ln_bwd_launch<false, false, false, false, false>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, nullptr,
+                                                                  0.f, fs2_make_drop(0.f, 0), stream);
   // partial is [nblk][2][C]: columns [0, C) -> dgamma, [C, 2C) -> dbeta
-  if (!dgamma && !dbeta) return 0;  // the caller finishes the partial sums with fs2hip_reduce_rows_multi
-  return fs2_reduce_rows(partial, nblk, 2 * C, 2LL * C, dgamma, C, dbeta, s);
+  if (rc || (!dgamma && !dbeta)) return rc;  // (neither: the caller finishes the partial sums with fs2hip_reduce_rows_multi)
+  return fs2_reduce_rows(partial, fs2hip_layernorm_bwd_blocks(M), 2 * C, 2LL * C, dgamma, C, dbeta, (hipStream_t)stream);
 }
 
+// partial is [nblk][3][C]; the caller finishes it with fs2hip_reduce_rows_multi
 extern "C" int fs2hip_layernorm_bwd_dz(const float* dy, const float* x, const float* gamma, const float* mean,
                                        const float* rstd, const float* dx_add, float* dx, float* dz, float dz_scale,
                                        float drop_p, unsigned long long drop_seed, const unsigned long long* drop_step,
                                        float* partial, int M, int C, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256 || !dz || !partial) return FS2HIP_EINVAL;
-  if (((uintptr_t)x % 16) || ((uintptr_t)dy % 16) || ((uintptr_t)dx % 16) || ((uintptr_t)dz % 16) || ((uintptr_t)gamma % 16))
-    return FS2HIP_EINVAL;
-  if (dx_add && ((uintptr_t)dx_add % 16)) return FS2HIP_EINVAL;
-  const int nblk = fs2hip_layernorm_bwd_blocks(M);
-  hipStream_t s = (hipStream_t)stream;
-  const Fs2Drop drop = fs2_make_drop(drop_p, drop_seed, drop_step);
-  const int nch = (C / 4 + 63) / 64;
-  switch (nch) {
-    case 1: ln_bwd_kernel<1, true><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale, drop, ln_bwd_rows(M)); break;
-    case 2: ln_bwd_kernel<2, true><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale, drop, ln_bwd_rows(M)); break;
-    default: ln_bwd_kernel<4, true><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale, drop, ln_bwd_rows(M)); break;
-  }
-  FS2_LAUNCH_CHECK();
-  return 0;  // partial is [nblk][3][C]; the caller finishes it with fs2hip_reduce_rows_multi
+  if (!ln_shape_ok(M, C) || !dz || !partial) return FS2HIP_EINVAL;
+  if (!ln_al16(x) || !ln_al16(dy) || !ln_al16(dx) || !ln_al16(dz) || !ln_al16(gamma) || !ln_al16(dx_add)) return FS2HIP_EINVAL;
+  return ln_bwd_launch<true, false, false, false, false>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale,
+                                                         fs2_make_drop(drop_p, drop_seed, drop_step), stream);
 }
 
 // The same backward with bf16 on either side of it.  flags bit 0: dy is bf16; bit 1: dz is bf16.  dz == NULL: no
@@ -345,37 +314,18 @@ extern "C" int fs2hip_layernorm_bwd_x(const void* dy, const float* x, const floa
                                       const float* rstd, const float* dx_add, float* dx, void* dz, float dz_scale,
                                       float drop_p, unsigned long long drop_seed, const unsigned long long* drop_step,
                                       float* partial, int M, int C, int flags, void* stream) {
-  if (M <= 0 || C <= 0 || (C % 4) || C > LN_MAX_CH * 256 || !partial) return FS2HIP_EINVAL;
+  if (!ln_shape_ok(M, C) || !partial) return FS2HIP_EINVAL;
   const bool dyb = flags & 1, zb = flags & 2;
-  if (((uintptr_t)x % 16) || ((uintptr_t)dy % (dyb ? 8 : 16)) || ((uintptr_t)dx % 16) || ((uintptr_t)gamma % 16)) return FS2HIP_EINVAL;
-  if (dz && ((uintptr_t)dz % (zb ? 8 : 16))) return FS2HIP_EINVAL;
-  if (dx_add && ((uintptr_t)dx_add % 16)) return FS2HIP_EINVAL;
-  const int nblk = fs2hip_layernorm_bwd_blocks(M);
-  hipStream_t s = (hipStream_t)stream;
+  if (!ln_al16(x) || ((uintptr_t)dy % (dyb ? 8 : 16)) || !ln_al16(dx) || !ln_al16(gamma)) return FS2HIP_EINVAL;
+  if (((uintptr_t)dz % (zb ? 8 : 16)) || !ln_al16(dx_add)) return FS2HIP_EINVAL;
   const Fs2Drop drop = fs2_make_drop(dz ? drop_p : 0.f, drop_seed, drop_step);
-  const int nch = (C / 4 + 63) / 64;
-#define FS2_LNB(N_, DZ_, DYB_, ZB_) \
-  ln_bwd_kernel<N_, DZ_, DYB_, ZB_><<<dim3(nblk), dim3(256), 0, s>>>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale, drop, ln_bwd_rows(M))
-#define FS2_LNB_N(N_)                                      \
-  do {                                                     \
-    if (!dz) {                                             \
-      if (dyb) FS2_LNB(N_, false, true, false);            \
-      else FS2_LNB(N_, false, false, false);               \
-    } else if (dyb) {                                      \
-      if (zb) FS2_LNB(N_, true, true, true);               \
-      else FS2_LNB(N_, true, true, false);                 \
-    } else {                                               \
-      if (zb) FS2_LNB(N_, true, false, true);              \
-      else FS2_LNB(N_, true, false, false);                \
-    }                                                      \
-  } while (0)
-  switch (nch) {
-    case 1: FS2_LNB_N(1); break;
-    case 2: FS2_LNB_N(2); break;
-    default: FS2_LNB_N(4); break;
-  }
-#undef FS2_LNB_N
-#undef FS2_LNB
-  FS2_LAUNCH_CHECK();
-  return 0;
+  return fs2_pick_bool(dyb, [&](auto dyb_c) {
+    if (!dz)  // no second output: its type does not matter
+      return ln_bwd_launch<false, dyb_c, false, false, false>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz,
+                                                              dz_scale, drop, stream);
+    return fs2_pick_bool(zb, [&](auto zb_c) {
+      return ln_bwd_launch<true, dyb_c, zb_c, false, false>(dy, x, gamma, mean, rstd, dx_add, dx, partial, M, C, dz, dz_scale,
+                                                            drop, stream);
+    });
+  });
 }

@@ -3,12 +3,14 @@
 
     python tools/device_code_diff.py OLD_OBJ_DIR NEW_OBJ_DIR [object names ...]
 
-Both directories hold the objects ``fastspeech2_lightning_amd.build`` leaves in ``fastspeech2_lightning_amd/build/``
-(default: the GEMM objects).  From every object the gfx950 code object is taken out of the ``.hip_fatbin`` section
-(llvm-objcopy, clang-offload-bundler) and disassembled (llvm-objdump -d); the two disassemblies are compared PER SYMBOL --
-the order in which templates are first used may reorder the kernels inside a code object, so addresses are dropped and
-only each symbol's instruction text and encodings count.  Prints one line per object; exits non-zero when a symbol is
-missing on either side or its instructions differ.  A host-side refactor must come out identical."""
+Both directories hold the objects ``fastspeech2_lightning_amd.build`` leaves in ``fastspeech2_lightning_amd/build/``.
+Without names every object present in both directories is compared (one that only one of them has is named, nothing
+more); the name ``gemm-family`` stands for the eight GEMM objects.  From every object the gfx950 code object is taken
+out of the ``.hip_fatbin`` section (llvm-objcopy, clang-offload-bundler) and disassembled (llvm-objdump -d); the two
+disassemblies are compared PER SYMBOL -- the order in which templates are first used may reorder the kernels inside a
+code object, so addresses are dropped and only each symbol's instruction text and encodings count (zero padding behind a
+symbol's last instruction is dropped too).  Prints one line per object; exits non-zero when a symbol is missing on
+either side or its instructions differ.  A host-side refactor must come out identical."""
 from __future__ import annotations
 
 import os
@@ -36,6 +38,9 @@ def tool(name: str) -> str:
 def disassemble(obj: Path, tmp: Path) -> dict[str, list[str]]:
     """{symbol: [instruction text + encoding, ...]} of the object's gfx950 code object"""
     fatbin, co = tmp / (obj.stem + ".fatbin"), tmp / (obj.stem + ".co")
+    sections = subprocess.run([tool("llvm-objdump"), "-h", str(obj)], check=True, capture_output=True, text=True).stdout
+    if ".hip_fatbin" not in sections:  # a host-only source
+        return {}
     subprocess.run([tool("llvm-objcopy"), f"--dump-section=.hip_fatbin={fatbin}", str(obj)], check=True)
     subprocess.run([tool("clang-offload-bundler"), "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fatbin}",
                     f"--output={co}"], check=True)
@@ -76,6 +81,9 @@ def disassemble(obj: Path, tmp: Path) -> dict[str, list[str]]:
         g = re.match(r"s_getpc_b64 s\[(\d+):\d+\]$", insn)
         getpc = f"s{g.group(1)}" if g else None
         cur.append(insn + " | " + enc)
+    for insns in symbols.values():  # a single zero word of the same padding is printed as an instruction, not as "..."
+        while insns and insns[-1].endswith("| 00000000"):
+            insns.pop()
     return symbols
 
 
@@ -84,8 +92,13 @@ def main(argv: list[str]) -> int:
         print(__doc__)
         return 2
     old, new = Path(argv[1]), Path(argv[2])
-    names = argv[3:] or GEMM_OBJECTS
+    names = [n for arg in argv[3:] for n in (GEMM_OBJECTS if arg == "gemm-family" else [arg])]
     bad = 0
+    if not names:
+        have = [{p.stem for p in d.glob("*.o")} for d in (old, new)]
+        names = sorted(have[0] & have[1])
+        for only in sorted(have[0] ^ have[1]):
+            print(f"{only}: in one build only, not compared")
     with tempfile.TemporaryDirectory() as t:
         (Path(t) / "old").mkdir()
         (Path(t) / "new").mkdir()
@@ -103,7 +116,7 @@ def main(argv: list[str]) -> int:
                     for s in syms[:10]:
                         print(f"    {label}: {s}")
             else:
-                print(f"{name}: identical -- {len(b)} symbols, {n_insn} instructions")
+                print(f"{name}: identical -- {len(b)} symbols, {n_insn} instructions" if b else f"{name}: no device code")
     return 1 if bad else 0
 
 
