@@ -153,7 +153,9 @@ def build_parser() -> argparse.ArgumentParser:
     sy.add_argument("--pitch-control", type=float, default=1.0, help="multiplies the predicted pitch (InferenceControl.pitch)")
     sy.add_argument("--energy-control", type=float, default=1.0, help="multiplies the predicted energy (InferenceControl.energy)")
     sy.add_argument("-S", "--style-reference", type=Path, default=None,
-                    help="a .pt file holding a [n_mels, frames] mel in the preprocessor's layout (GST models only)")
+                    help="a .pt file holding a [n_mels, frames] mel in the preprocessor's layout (GST models only).  A filelist's "
+                         "style_reference column names one per row (relative to the filelist, or absolute) and overrides this; "
+                         "rows without one take this")
     sy.add_argument("-T", "--teacher-forcing-directory", type=Path, default=None,
                     help="ADVANCED. preprocessed folder with spec and duration / attn folders to teacher-force the outputs")
     sy.add_argument("-b", "--batch-size", type=int, default=4)
@@ -726,6 +728,58 @@ def duration_file_names(dataset, out_dir) -> list:
                              e.get("language") or "default", "duration.pt")) for e in dataset.entries]
 
 
+def style_references(entries: list, shared, filelist, n_mels: int) -> tuple:
+    """The style references of ``fs2l synthesize``: ``-S`` (``shared``, one ``.pt`` for the run) and the filelist's
+    ``style_reference`` column (one ``.pt`` per row, relative to the filelist or absolute).  A row's entry overrides ``-S``;
+    rows without one take ``-S``; a row without one on a run where other rows have one and there is no ``-S`` is an error
+    that names it.  Files are loaded once per path and must hold a ``[n_mels, frames]`` mel.
+
+    Returns ``(what SynthesisDataset takes as style_reference, [every row's source])``: None / the shared mel / one mel per
+    entry (rows of one path share one object), and ``"own file"`` / ``"shared file"`` / None per entry."""
+    cache = {}
+
+    def load(path, what):
+        path = Path(path)
+        if path.suffix != ".pt":
+            raise SystemExit(f"{what} {path}: expected a .pt file holding a [n_mels, frames] mel; turning audio into a mel "
+                             "needs the parent toolkit's preprocessor")
+        key = str(path.resolve())
+        if key not in cache:
+            try:
+                ref = torch.load(path, map_location="cpu", weights_only=True)
+            except FileNotFoundError:
+                raise SystemExit(f"{what} {path}: no such file") from None
+            shape = list(ref.shape) if torch.is_tensor(ref) else type(ref).__name__
+            if not torch.is_tensor(ref) or ref.dim() not in (2, 3) or (ref.dim() == 3 and ref.shape[0] != 1) \
+                    or ref.shape[-2] != n_mels or ref.shape[-1] < 1:
+                raise SystemExit(f"{what} {path}: expected a [n_mels = {n_mels}, frames] mel, got {shape}")
+            cache[key] = ref
+        return cache[key]
+
+    own = [e.get("style_reference") for e in entries]
+    if not any(own):
+        if shared is None:
+            return None, [None] * len(entries)
+        # (one reference for the run: loaded as it is, SynthesisDataset checks it)
+        return torch.load(shared, map_location="cpu", weights_only=True), ["shared file"] * len(entries)
+    base = Path(filelist).parent if filelist is not None else Path(".")
+    shared_ref = load(shared, "--style-reference") if shared is not None else None
+    refs, sources = [], []
+    for i, (e, name) in enumerate(zip(entries, own)):
+        if name:
+            path = Path(name)
+            refs.append(load(path if path.is_absolute() else base / path,
+                             f"style_reference of row {i + 1} ({e.get('basename')!r})"))
+            sources.append("own file")
+        elif shared_ref is not None:
+            refs.append(shared_ref)
+            sources.append("shared file")
+        else:
+            raise SystemExit(f"row {i + 1} ({e.get('basename')!r}) of {filelist} has no style_reference and there is no "
+                             "--style-reference (-S) to fall back on: other rows name one")
+    return refs, sources
+
+
 def synthesize_command(args) -> int:
     """``fs2l synthesize`` (reference ``fs2/cli/synthesize.py:466-700``): checkpoint + text -> ``.pt`` spectrograms in
     ``OUTPUT_DIR/synthesized_spec/``, one GPU.  Argument errors come before anything expensive is loaded."""
@@ -757,11 +811,9 @@ def synthesize_command(args) -> int:
     if config.model.target_text_representation_level == L.characters and args.text_representation != "characters":
         raise ValueError(f"Your model was trained on {config.model.target_text_representation_level} but you provided "
                          f"{args.text_representation} which is incompatible.")
-    style = None
-    if args.style_reference is not None:
-        style = torch.load(args.style_reference, map_location="cpu", weights_only=True)
     entries = synthesis_entries(args.texts, args.filelist, args.language, args.speaker, args.duration_control, model,
                                 args.text_representation)
+    style, style_sources = style_references(entries, args.style_reference, args.filelist, config.preprocessing.audio.n_mels)
     dataset = SynthesisDataset(entries, config, model.lang2id, model.speaker2id,
                                teacher_forcing_dir=args.teacher_forcing_directory, style_reference=style,
                                attn_prior=attn_prior_mode(args, config)["attn_prior"])
@@ -777,6 +829,10 @@ def synthesize_command(args) -> int:
             "batches": synthesis_batches(dataset.token_counts, args.batch_size, sort),
             "entries": [{k: e.get(k) for k in ("basename", "language", "speaker", "duration_control")} for e in entries],
             "files": [] if args.scores_only else synthesis_file_names(dataset, args.output_dir, global_step)}
+        if config.model.use_global_style_token_module:
+            # where every row's style comes from: style token 0, the -S file, the row's own file, or (teacher forcing
+            # without a reference) the row's target mel
+            plan["style_sources"] = [s or ("target" if dataset.teacher_forcing else "token") for s in style_sources]
         if scores is not None:
             plan["scores_file"] = str(scores.path)
             for e, cov in zip(plan["entries"], coverage_scores(dataset.tokens)):

@@ -4,6 +4,8 @@
 //   conv2d_s2       : 3x3, stride 2, pad 1, no bias, channels-last [B][H][W][C]; weights [kh][kw][ci][co]
 //   gru_gate        : r, z, n gates + state update of one time step (the two matmuls run on the GEMM kernel)
 //   gst_attn        : softmax(q k^T / sqrt(d_k)) v of one query per utterance against the style tokens
+//   gru_last_state  : the whole inference recurrence in one launch, a step count per utterance (length-aware inference)
+//   conv_s2_lens    : the row counts an utterance keeps after each stride-2 convolution
 #include "common.h"
 
 namespace {
@@ -241,6 +243,82 @@ __global__ void gru_gate_bwd_kernel(const float* __restrict__ dh, const float* _
   dhprev[i] = d * z;
 }
 
+// ---- the whole inference recurrence in one launch, a step count per utterance (fs2hip_gru_last_state) ----
+// One workgroup per utterance, one thread per gate row: thread j keeps row j of w_hh [3U][U] in registers for all steps
+// (128 VGPRs; loaded once), h [U] and the 3U recurrent sums live in LDS.  A step is: every thread's dot product of its row
+// with h (k ascending, one fmaf chain -- the result of a row is a function of that utterance's gi alone, whatever the
+// batch), a barrier, the gates on the first U threads, a barrier.  gi rows at and beyond the utterance's step count are
+// never addressed.  The step's three gi values are requested before the dot product and used after it.
+constexpr int GRU_U = 128;
+__global__ __launch_bounds__(3 * GRU_U) void gru_last_state_kernel(const float* __restrict__ gi,
+                                                                    const float* __restrict__ w_hh,
+                                                                    const float* __restrict__ b_hh,
+                                                                    const int* __restrict__ steps,
+                                                                    float* __restrict__ h_out, int T) {
+  constexpr int U = GRU_U;
+  __shared__ __attribute__((aligned(16))) float sh[U];
+  __shared__ float sgh[3 * U];
+  const int b = blockIdx.x, j = threadIdx.x;
+  int n = steps[b];
+  n = n < 0 ? 0 : (n > T ? T : n);
+  if (n == 0) {  // (uniform over the workgroup)
+    if (j < U) h_out[(long long)b * U + j] = 0.f;
+    return;
+  }
+  float w[U];
+  const f32x4* wrow = reinterpret_cast<const f32x4*>(w_hh + (long long)j * U);
+#pragma unroll
+  for (int k4 = 0; k4 < U / 4; ++k4) {
+    const f32x4 v = wrow[k4];
+    w[4 * k4] = v[0]; w[4 * k4 + 1] = v[1]; w[4 * k4 + 2] = v[2]; w[4 * k4 + 3] = v[3];
+  }
+  const float bias = b_hh[j];
+  float h = 0.f;  // thread j < U: element j of the state
+  if (j < U) sh[j] = 0.f;
+  __syncthreads();
+  const float* gib = gi + (long long)b * T * 3 * U;
+  const f32x4* sh4 = reinterpret_cast<const f32x4*>(sh);
+  for (int t = 0; t < n; ++t) {
+    float gr = 0.f, gz = 0.f, gn = 0.f;
+    if (j < U) {
+      const float* g = gib + (long long)t * 3 * U;
+      gr = g[j]; gz = g[U + j]; gn = g[2 * U + j];
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int k4 = 0; k4 < U / 4; ++k4) {
+      const f32x4 hv = sh4[k4];
+      acc = fmaf(hv[0], w[4 * k4], acc);
+      acc = fmaf(hv[1], w[4 * k4 + 1], acc);
+      acc = fmaf(hv[2], w[4 * k4 + 2], acc);
+      acc = fmaf(hv[3], w[4 * k4 + 3], acc);
+    }
+    sgh[j] = acc + bias;
+    __syncthreads();
+    if (j < U) {
+      const float r = fs2_sigmoid(gr + sgh[j]);
+      const float z = fs2_sigmoid(gz + sgh[U + j]);
+      const float c = tanhf(gn + r * sgh[2 * U + j]);
+      h = (1.f - z) * c + z * h;
+      sh[j] = h;
+    }
+    __syncthreads();
+  }
+  if (j < U) h_out[(long long)b * U + j] = h;
+}
+
+// table[l][b], l = 0 .. n: the row counts an utterance of lens[b] frames has after l stride-2 convolutions
+__global__ void conv_s2_lens_kernel(const int* __restrict__ lens, int* __restrict__ table, int B, int n) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  int v = lens[b];
+  table[b] = v;
+  for (int l = 1; l <= n; ++l) {
+    v = v > 0 ? (v - 1) / 2 + 1 : 0;
+    table[(long long)l * B + b] = v;
+  }
+}
+
 // ---- style-token attention: one query per utterance, NT tokens, HEADS x 64 dims (one wavefront per head) ----
 constexpr int GST_MAX_TOKENS = 32;
 __global__ __launch_bounds__(256) void gst_attn_fwd_kernel(const float* __restrict__ q, const float* __restrict__ k,
@@ -384,6 +462,22 @@ extern "C" int fs2hip_gru_gate_bwd(const float* dh, const float* gates, const fl
                                    float* dgh, float* dhprev, int B, int U, void* stream) {
   if (B <= 0 || U <= 0) return FS2HIP_EINVAL;
   gru_gate_bwd_kernel<<<dim3((B * U + 255) / 256), dim3(256), 0, S_>>>(dh, gates, hprev, dgi, dgi_stride, dgh, dhprev, B, U);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_gru_last_state(const float* gi, const float* w_hh, const float* b_hh, const int* steps, float* h_out,
+                                     int B, int T, int U, void* stream) {
+  if (!gi || !w_hh || !b_hh || !steps || !h_out || B <= 0 || T <= 0 || U != GRU_U || ((uintptr_t)w_hh % 16))
+    return FS2HIP_EINVAL;
+  gru_last_state_kernel<<<dim3(B), dim3(3 * GRU_U), 0, S_>>>(gi, w_hh, b_hh, steps, h_out, T);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_conv_s2_lens(const int* lens, int* table, int B, int n, void* stream) {
+  if (!lens || !table || B <= 0 || n < 0 || n > 8) return FS2HIP_EINVAL;
+  conv_s2_lens_kernel<<<dim3((B + 255) / 256), dim3(256), 0, S_>>>(lens, table, B, n);
   FS2_LAUNCH_CHECK();
   return 0;
 }

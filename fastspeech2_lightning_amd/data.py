@@ -753,7 +753,7 @@ def synthesis_entries(texts, filelist, language, speaker, duration_control, mode
                 e = {"basename": r.get("basename") or truncate_basename(slugify(text)), key: text,
                      "language": language or r.get("language") or default_language,
                      "speaker": speaker or r.get("speaker") or default_speaker}
-                for col in ("character_tokens", "phone_tokens"):
+                for col in ("character_tokens", "phone_tokens", "style_reference"):
                     if r.get(col):
                         e[col] = r[col]
                 data.append(e)
@@ -773,6 +773,24 @@ def synthesis_entries(texts, filelist, language, speaker, duration_control, mode
         d["is_last_input_chunk"] = True
         d["duration_control"] = duration_control if duration_control else 1.0
     return data
+
+
+def _style_mel(ref, n_mels: int, what: str) -> torch.Tensor:
+    """A ``[n_mels, frames]`` mel (the preprocessor's layout; a leading axis of 1 is dropped) as ``[frames, n_mels]`` fp32."""
+    ref = torch.as_tensor(ref, dtype=torch.float32)
+    ref = ref.squeeze(0) if ref.dim() == 3 else ref
+    if ref.dim() != 2 or ref.shape[0] != n_mels or ref.shape[1] < 1:
+        raise ValueError(f"{what} must be a [n_mels = {n_mels}, frames] mel, got {list(ref.shape)}")
+    return ref.transpose(0, 1).contiguous()
+
+
+def style_reference_lens(items: list[dict]) -> Optional[torch.Tensor]:
+    """[B] int32, every item's own style-reference frame count, when the items' references are not all one object (they are
+    then zero-padded to the longest by ``collate``); None for one shared reference or none."""
+    refs = [item.get("mel_style_reference") for item in items]
+    if torch.is_tensor(refs[0]) and any(r is not refs[0] for r in refs):
+        return torch.tensor([len(r) for r in refs], dtype=torch.int32)
+    return None
 
 
 def synthesis_batches(token_counts, batch_size: int, sort: bool = True) -> list[list[int]]:
@@ -803,8 +821,11 @@ class SynthesisDataset(torch.utils.data.Dataset):
     on stderr, and an utterance left without a token is an error that names it.
 
     ``style_reference``: a ``[n_mels, frames]`` mel (the preprocessor's spectrogram layout), attached to every item as
-    ``mel_style_reference`` ``[frames, n_mels]``; refused by a model without the GST module.  Every text is encoded in the
-    constructor: ``token_counts`` is what ``synthesis_batches`` takes."""
+    ``mel_style_reference`` ``[frames, n_mels]``; refused by a model without the GST module.  It may also be one such mel
+    per entry -- a sequence in entry order, or a mapping by basename: every item then carries its own reference, and a
+    batch of them carries their frame counts (``style_reference_lens``).  Entries given the same object share
+    it; when all do, this is the single shared reference again.  Every text is encoded in the constructor:
+    ``token_counts`` is what ``synthesis_batches`` takes."""
 
     def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, teacher_forcing_dir=None,
                  style_reference=None, text_processor=None, attn_prior: str = "files"):
@@ -827,16 +848,18 @@ class SynthesisDataset(torch.utils.data.Dataset):
         if self.use_pfs and not self.teacher_forcing:
             raise ValueError("a phonological_features model needs feature vectors that only the parent toolkit computes: "
                              "free synthesis is not possible here (teacher forcing loads the stored pfs.pt)")
-        self.style = None
+        self.style, self.styles = None, None
         if style_reference is not None:
             if not m.use_global_style_token_module:
                 raise ValueError("a style reference needs a model trained with the global style token module "
                                  "(model.use_global_style_token_module)")
-            ref = torch.as_tensor(style_reference, dtype=torch.float32)
-            ref = ref.squeeze(0) if ref.dim() == 3 else ref
-            if ref.dim() != 2 or ref.shape[0] != audio.n_mels or ref.shape[1] < 1:
-                raise ValueError(f"style reference must be a [n_mels = {audio.n_mels}, frames] mel, got {list(ref.shape)}")
-            self.style = ref.transpose(0, 1).contiguous()
+            if isinstance(style_reference, dict) or (isinstance(style_reference, (list, tuple)) and all(
+                    r is None or torch.is_tensor(r) or isinstance(r, np.ndarray) for r in style_reference)):
+                self.styles = self._per_entry_styles(style_reference, entries, audio.n_mels)
+                if all(s is self.styles[0] for s in self.styles):
+                    self.style, self.styles = self.styles[0], None   # one object for all: the shared reference's path
+            else:
+                self.style = _style_mel(style_reference, audio.n_mels, "style reference")
         tok_key, raw_key = ("character_tokens", "characters") if self.chars else ("phone_tokens", "phones")
         self.tokens, dropped = [], 0
         for e in entries:
@@ -861,6 +884,28 @@ class SynthesisDataset(torch.utils.data.Dataset):
             print(f"{dropped} input symbol(s) are not in the model's symbol table and were dropped", file=sys.stderr)
 
     _load = FeatureDataset._load
+
+    @staticmethod
+    def _per_entry_styles(refs, entries, n_mels) -> list:
+        """One ``[frames, n_mels]`` reference per entry from a sequence (in entry order) or a mapping by basename.  Entries
+        given the same object share one converted tensor, so "all one object" survives the conversion."""
+        if isinstance(refs, dict):
+            missing = [e.get("basename") for e in entries if e.get("basename") not in refs]
+            if missing:
+                raise ValueError(f"style references: no entry for utterance {missing[0]!r}"
+                                 + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+            refs = [refs[e["basename"]] for e in entries]
+        if len(refs) != len(entries):
+            raise ValueError(f"style references: {len(refs)} given for {len(entries)} utterances")
+        done, out = {}, []
+        for e, ref in zip(entries, refs):
+            if ref is None:
+                raise ValueError(f"style references: utterance {e.get('basename')!r} has none (every utterance needs one "
+                                 "when any has its own)")
+            if id(ref) not in done:
+                done[id(ref)] = _style_mel(ref, n_mels, f"style reference of utterance {e.get('basename')!r}")
+            out.append(done[id(ref)])
+        return out
 
     def __len__(self):
         return len(self.entries)
@@ -891,7 +936,8 @@ class SynthesisDataset(torch.utils.data.Dataset):
                 pfs = self._load(bn, speaker, language, "pfs", "pfs.pt")
         last = item.get("is_last_input_chunk")
         return {
-            "mel": mel, "mel_style_reference": self.style, "duration": duration,
+            "mel": mel, "mel_style_reference": self.style if self.styles is None else self.styles[index],
+            "duration": duration,
             "duration_control": item.get("duration_control", 1.0), "pfs": pfs, "text": self.tokens[index],
             "raw_text": item.get("characters", item.get("phones", "text")), "basename": bn,
             "speaker": speaker, "speaker_id": self.speaker2id.get(speaker, 0) if not m.multispeaker else self.speaker2id[speaker],

@@ -154,6 +154,8 @@ SIGNATURES = {
     "fs2hip_utterance_losses": "pipppiifpfpip",  # (the first: const Fs2ScoreMember*, a ctypes array)
     "fs2hip_attn_prior": "pppiiifp",
     "fs2hip_pack_rows": None,  # (const Fs2PackMember*, int, int, void*): set below
+    "fs2hip_gru_last_state": "pppppiiip",
+    "fs2hip_conv_s2_lens": "ppiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -2432,6 +2434,36 @@ def gru_gate_bwd(dh, gates, hprev, dgi_t, dgi_stride, U, dgh=None):
     _ok(lib().fs2hip_gru_gate_bwd(_p(dh), _p(gates), _p(hprev), dgi_t.data_ptr(), dgi_stride, _p(dgh), _p(dhprev), B, U,
                                   _stream()), "gru_gate_bwd")
     return dgh, dhprev
+
+
+def gru_last_state(gi, w_hh, b_hh, steps):
+    """The whole inference recurrence of ``nn.GRU`` (gate order r, z, n; h0 = 0) in ONE launch: ``gi`` [B, T, 3U] (input
+    projections incl. ``b_ih``), ``w_hh`` [3U, U], ``b_hh`` [3U], ``steps`` [B] int32 in GPU memory -> [B, U], row b after
+    ``clamp(steps[b], 0, T)`` steps (0: zeros).  Rows of ``gi`` at and beyond a row's count are never read.  U = 128 only."""
+    _chk(gi, name="gi"); _chk(w_hh, name="w_hh"); _chk(b_hh, name="b_hh"); _chk(steps, torch.int32, "steps")
+    _req(gi.dim() == 3 and gi.numel() > 0, f"gru_last_state: gi must be a non-empty [B, T, 3U], got {tuple(gi.shape)}")
+    B, T, G = gi.shape
+    U = w_hh.shape[-1]
+    _req(U == 128, f"gru_last_state: U = {U}, only 128 (the reference encoder's GRU) is built")
+    _req(w_hh.shape == (3 * U, U) and b_hh.shape == (3 * U,) and G == 3 * U,
+         f"gru_last_state: gi {tuple(gi.shape)}, w_hh {tuple(w_hh.shape)}, b_hh {tuple(b_hh.shape)} do not fit U = {U}")
+    _req(steps.numel() == B, f"gru_last_state: steps has {steps.numel()} entries for {B} utterances")
+    _req(w_hh.data_ptr() % 16 == 0, "gru_last_state: w_hh must be 16-byte aligned")
+    h = torch.empty(B, U, device=gi.device, dtype=torch.float32)
+    _ok(lib().fs2hip_gru_last_state(_p(gi), _p(w_hh), _p(b_hh), _p(steps), _p(h), B, T, U, _stream()), "gru_last_state")
+    return h
+
+
+def conv_s2_lens(lens, n):
+    """[n + 1, B] int32: row l holds the rows each utterance keeps after l stride-2 convolutions (kernel 3, pad 1):
+    row 0 = ``lens``, then ``(L - 1) // 2 + 1`` (0 stays 0).  ``lens`` [B] int32 stays in GPU memory; n = 0 .. 8."""
+    _chk(lens, torch.int32, "lens")
+    n = int(n)
+    _req(lens.dim() == 1 and lens.numel() > 0, f"conv_s2_lens: lens must be a non-empty vector, got {tuple(lens.shape)}")
+    _req(0 <= n <= 8, f"conv_s2_lens: n = {n} (0 to 8)")
+    table = torch.empty(n + 1, lens.numel(), device=lens.device, dtype=torch.int32)
+    _ok(lib().fs2hip_conv_s2_lens(_p(lens), _p(table), lens.numel(), n, _stream()), "conv_s2_lens")
+    return table
 
 
 def gst_attn_fwd(q, k, v, heads):

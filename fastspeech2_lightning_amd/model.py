@@ -605,12 +605,14 @@ class FastSpeech2(_Base):
     def prepare_batch(self, batch):
         """Moves the collated batch to the GPU with the dtypes the kernels take."""
         b = dict(batch)
-        for k in ("text", "src_lens", "mel_lens", "speaker_id", "language_id"):
+        for k in ("text", "src_lens", "mel_lens", "speaker_id", "language_id", "style_reference_lens"):
             if b.get(k) is not None:
                 b[k] = self._dev(b[k], torch.int32)
         for k in ("mel", "pitch", "energy"):
             if b.get(k) is not None:
                 b[k] = self._dev(b[k], torch.float32)
+        if b.get("style_reference_lens") is not None and b.get("mel_style_reference") is batch.get("mel"):
+            b["mel_style_reference"] = b["mel"]  # every utterance's own target mel as its style: uploaded once
         if self.use_pfs and b.get("pfs") is not None and b["pfs"].shape[-1] == N_PHONOLOGICAL_FEATURES:
             # feature rows padded with zero columns to a multiple of 4 floats (the GEMM reads 16-byte pieces)
             pfs = self._dev(b["pfs"], torch.float32)
@@ -653,6 +655,8 @@ class FastSpeech2(_Base):
         reads them into an utterance's last frames: with the flag their inputs' padded rows are zeroed on the device
         first (``hip.zero_tail_rows``, lengths never visit the host).  Without it not one launch changes.  Training and
         validation keep the reference's definition (BatchNorm statistics and loss denominators include padding)."""
+        if batch.get("style_reference_lens") is not None:
+            self._check_style_reference_lens(batch, inference)
         if exact_lengths:
             if not inference:
                 raise ValueError("exact_lengths=True goes with inference=True: training and validation forwards keep the "
@@ -672,6 +676,27 @@ class FastSpeech2(_Base):
                 return self._forward(batch, control, inference)
             finally:
                 self.env.exact = False
+
+    def _check_style_reference_lens(self, batch, inference):
+        """``style_reference_lens`` [B] (host or device): how many frames of every row of ``mel_style_reference`` [B, T_ref,
+        n_mels] are the reference -- the style encoder then gives each row what its own frames give alone
+        (``StyleEncoder.fwd(mel, lens)``).  The values are checked here when the vector arrives on the host."""
+        lens, ref = batch["style_reference_lens"], batch.get("mel_style_reference")
+        if self.gst is None:
+            raise ValueError("style_reference_lens needs a model with the global style token module "
+                             "(model.use_global_style_token_module)")
+        if not inference or self.training:
+            raise ValueError("style_reference_lens goes with inference=True on a model in eval mode (model.eval()): training "
+                             "and validation take the style from the target mels, as the reference does")
+        if not torch.is_tensor(ref) or ref.dim() != 3:
+            raise ValueError("style_reference_lens needs a mel_style_reference tensor of [B, T_ref, n_mels]")
+        if not torch.is_tensor(lens) or lens.dim() != 1 or lens.numel() != ref.shape[0] or lens.is_floating_point():
+            raise ValueError(f"style_reference_lens must be an integer vector of {ref.shape[0]} entries (one per row of "
+                             "mel_style_reference)")
+        if not lens.is_cuda:
+            lo, hi = int(lens.min()), int(lens.max())
+            if lo < 1 or hi > ref.shape[1]:
+                raise ValueError(f"style_reference_lens must lie in 1 .. T_ref = {ref.shape[1]}, got {lo} .. {hi}")
 
     def _forward(self, batch, control=None, inference=False):
         H.set_precision(self.precision)
@@ -706,7 +731,14 @@ class FastSpeech2(_Base):
             # kernels are small and latency-bound) and is joined where its vector is added.
             ref_mel = batch.get("mel_style_reference")
             with self.env.side(batch.get("mel"), ref_mel if torch.is_tensor(ref_mel) else None):
-                if inference and torch.is_tensor(ref_mel):
+                if inference and torch.is_tensor(ref_mel) and batch.get("style_reference_lens") is not None:
+                    # every row's style from its own frames (the encoder zeroes the padded rows of what it is given: the
+                    # caller's tensor is not written to)
+                    ref_dev = self._dev(ref_mel, torch.float32)
+                    if ref_dev is ref_mel or ref_dev.data_ptr() == ref_mel.data_ptr():
+                        ref_dev = ref_dev.clone()
+                    style, _ = self.gst.fwd(ref_dev, batch["style_reference_lens"])
+                elif inference and torch.is_tensor(ref_mel):
                     style, _ = self.gst.fwd(self._dev(ref_mel, torch.float32))
                 elif inference and not teacher_forcing:
                     style = self.gst.condition_on_gst_tokens(B)

@@ -851,7 +851,11 @@ class StyleEncoder:
         w, b = self.lin[name]
         return self.S.p(w), self.S.p(b)
 
-    def fwd(self, mel):
+    def fwd(self, mel, lens=None):
+        """``lens`` ([B] int32 in GPU memory, eval mode only): every row's style is what its first ``lens[b]`` frames give
+        when they are encoded alone (``_fwd_lens``).  Without it: the reference's encoder, which reads the padding."""
+        if lens is not None:
+            return self._fwd_lens(mel, lens)
         S, env, U = self.S, self.env, self.U
         B, T, F = mel.shape
         x = mel.view(B, T, F, 1)
@@ -881,6 +885,34 @@ class StyleEncoder:
         style = H.linear_fwd(ctx, *self._lw("out"))
         return style, Ctx(conv=conv_saved, feat=feat, hs=hs, gates=gates, q=q, tk=tk, k=k, v=v, p=p, ctx=ctx,
                           shape=(B, Hh, Ww, C))
+
+    def _fwd_lens(self, mel, lens):
+        """The length-aware inference forward.  ``hip.conv_s2_lens`` gives every layer's row counts L_l; rows ``t >= L_l[b]``
+        of every convolution's input -- the mel included, IN PLACE -- are zeroed first (``hip.zero_tail_rows``): output row
+        ``t < L_{l+1}`` reads input rows up to ``2t + 1 <= L_l``, and row ``L_l`` is then the zero padding of the alone-run
+        (eval-mode BatchNorm is element-wise).  The GRU is ONE ``hip.gru_last_state`` launch that stops every row after
+        its own ``L_6`` steps.  Nothing is kept for a backward pass."""
+        S, env, U = self.S, self.env, self.U
+        if env.training:
+            raise ValueError("StyleEncoder.fwd: lens needs a model in eval mode (in train mode BatchNorm takes its "
+                             "statistics over the padded rows)")
+        B, T, F = mel.shape
+        table = H.conv_s2_lens(lens, len(self.convs))
+        x = mel.view(B, T, F, 1)
+        for i, (w, bn, c) in enumerate(self.convs):
+            H.zero_tail_rows(x, table[i], B, x.shape[1])
+            raw = H.conv2d_s2_fwd(x, S.p(w))
+            rows = raw.numel() // c
+            x = H.bn_act_fwd(raw.view(rows, c), bn.stats(None, False), "relu").view(raw.shape)
+        _, Hh, Ww, C = x.shape
+        gi = H.linear_fwd(x.view(B * Hh, Ww * C), S.p(self.wih), S.p(self.bih))      # rows (b, t)
+        ref = H.gru_last_state(gi.view(B, Hh, 3 * U), S.p(self.whh), S.p(self.bhh), table[len(self.convs)])
+        q = H.linear_fwd(ref, *self._lw("q"))
+        tk = H.act_apply(S.p(self.embs), "tanh")
+        k = H.linear_fwd(tk, *self._lw("k"))
+        v = H.linear_fwd(tk, *self._lw("v"))
+        _, ctx = H.gst_attn_fwd(q, k, v, self.HEADS)
+        return H.linear_fwd(ctx, *self._lw("out")), None
 
     def condition_on_gst_tokens(self, batch_size: int, index: int = 0):
         """reference ``fs2/gst/model.py:77-85`` (free inference without a reference mel): attention over the single

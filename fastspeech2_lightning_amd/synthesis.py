@@ -26,6 +26,12 @@ the offsets, so it leaves the GPU inside the copy that carries the spectrograms 
 ``exact_lengths`` is forced on: a score must not follow ``-b`` or the sort order.  Without a spectrogram writer (scores
 only) nothing is packed and the copy is the header alone.
 
+Style references of a GST model: one shared reference is encoded as the reference encodes it (the batch carries no
+lengths); per-entry references (``SynthesisDataset(style_reference=[...])``, the filelist's ``style_reference`` column) are
+padded to the batch's longest and travel with ``style_reference_lens``, so every row's style is what its own reference gives
+alone (``StyleEncoder.fwd(mel, lens)``).  A teacher-forced dataset without any reference, run with exact lengths (given or
+forced by scores), feeds every utterance's own target mel at its own length -- what the reference does at batch size 1.
+
 ``alignments`` (a ``data.AlignmentWriter``; ``fs2l synthesize --write-alignments``) adds what says which frames belong to
 which token: ``duration_rounded`` and the pitch and energy predictions, cut to every utterance's own lengths on the device
 by ONE ``hip.pack_rows`` call (two small launches) into an alignment block between the header and the spectrograms --
@@ -41,7 +47,7 @@ from typing import Optional
 import torch
 
 from . import hip as H
-from .data import collate, coverage_scores, synthesis_batches
+from .data import collate, coverage_scores, style_reference_lens, synthesis_batches
 from .model import LOSS_KEYS
 
 
@@ -100,6 +106,11 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
     n_mels = model.config.preprocessing.audio.n_mels
     learn_alignment = model.config.model.learn_alignment
     batches = synthesis_batches(dataset.token_counts, batch_size, sort)
+    # a GST model teacher-forced with exact lengths and no style reference: every utterance's own target mel at its own
+    # length is its style, as the reference takes it one utterance at a time (fs2/model.py:196-203)
+    own_target_style = bool(exact_lengths and getattr(dataset, "teacher_forcing", False)
+                            and getattr(model, "gst", None) is not None
+                            and getattr(dataset, "style", None) is None and getattr(dataset, "styles", None) is None)
     was_training = model.training
     model.eval()
     files, frames, alignment_files = [], 0, []
@@ -153,7 +164,10 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
             copy_stream = torch.cuda.Stream(device=device)
             slots = [_Slot(device) for _ in range(depth)]
             for i, positions in enumerate(batches):
-                cpu_batch = collate([dataset[j] for j in positions], learn_alignment=learn_alignment, pin_memory=True)
+                cpu_batch = collate_items([dataset[j] for j in positions], learn_alignment, pin_memory=True)
+                if own_target_style:
+                    cpu_batch["mel_style_reference"] = cpu_batch["mel"]
+                    cpu_batch["style_reference_lens"] = cpu_batch["mel_lens"]
                 out = model(cpu_batch, _copy_control(control), inference=True, exact_lengths=exact_lengths)
                 y = out[model.output_key]
                 B, Tm, C = y.shape
@@ -226,6 +240,17 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
         if teacher_forced and learn_alignment:
             res["duration_files"] = list(alignments.duration_files)
     return res
+
+
+def collate_items(items: list, learn_alignment: bool, pin_memory: bool = False) -> dict:
+    """``collate``'s batch of ``items``; when their style references are not all one object it also carries
+    ``style_reference_lens`` (``data.style_reference_lens``: every reference's own frame count in the zero-padded
+    ``mel_style_reference``), which makes ``FastSpeech2.forward`` encode every row as if it were alone."""
+    batch = collate(items, learn_alignment=learn_alignment, pin_memory=pin_memory)
+    lens = style_reference_lens(items)
+    if lens is not None:
+        batch["style_reference_lens"] = lens
+    return batch
 
 
 def _diff(cumulative: list) -> list:

@@ -667,6 +667,21 @@ typedef struct {
 } Fs2PackMember;
 int fs2hip_pack_rows(const Fs2PackMember* members, int n, int B, void* stream);
 
+/* Length-aware style encoding (inference): the reference encoder ignores lengths (fs2/gst/model.py:192), so a padded
+ * reference gives another style vector than the same reference alone.
+ *   gru_last_state  the whole nn.GRU recurrence (gate order r, z, n) from h0 = 0 in ONE launch, with a step count per
+ *                   utterance: gi [B][T][3U] (input projections incl. b_ih), w_hh [3U][U], b_hh [3U], steps [B] int32
+ *                   in device memory; h_out [B][U] = the state after clamp(steps[b], 0, T) steps.  A count of 0 writes
+ *                   zeros; rows of gi at and beyond an utterance's count are never read (they may hold NaN).  fp32; the
+ *                   recurrent sums add k ascending, so a row's result depends on that row's gi alone (bit-equal whatever
+ *                   the batch).  U must be 128, w_hh 16-byte aligned: FS2HIP_EINVAL otherwise, as for a null pointer
+ *                   or a non-positive extent.
+ *   conv_s2_lens    table [n + 1][B] int32: table[0] = lens, table[l + 1] = (table[l] - 1) / 2 + 1 where table[l] > 0,
+ *                   else 0 -- the rows an utterance keeps after l stride-2 convolutions.  0 <= n <= 8. */
+int fs2hip_gru_last_state(const float* gi, const float* w_hh, const float* b_hh, const int* steps, float* h_out, int B,
+                          int T, int U, void* stream);
+int fs2hip_conv_s2_lens(const int* lens, int* table, int B, int n, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
