@@ -130,6 +130,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="a model that learns its alignment: open no attn/*-attn-prior.pt file and compute the attention prior on the GPU "
                          "from each batch's lengths (fs2hip_attn_prior; this project's beta-binomial definition).  Ignored when "
                          "model.learn_alignment is false")
+    tr.add_argument("--style-lengths", action="store_true",
+                    help="a model with the global style token module: training and validation steps compute every utterance's "
+                         "style from its own mel_lens frames (padded rows zeroed in front of the style encoder's convolutions, "
+                         "BatchNorm statistics over the valid positions, the GRU stopped after each utterance's own steps), so "
+                         "the style does not follow the batch's or the bucket's padding (FastSpeech2.style_lengths).  Ignored "
+                         "when model.use_global_style_token_module is false")
     tr.add_argument("--dry-run", action="store_true", help="resolve config, filelists, look-up tables and the run directory, print the plan, touch no GPU "
                                                              "(with --bucket-lengths: also reads every item's lengths once and writes the cache "
                                                              "<run dir>/lengths.json, then prints the bucket table)")
@@ -141,6 +147,7 @@ def build_parser() -> argparse.ArgumentParser:
     bm.add_argument("--repetitions", type=int, default=300)
     bm.add_argument("--precision", default="32-true", choices=["32-true", "32-split", "bf16-mixed"])
     bm.add_argument("--compute-attn-prior", action="store_true", help="as for train: the batch carries no prior, the forward computes it")
+    bm.add_argument("--style-lengths", action="store_true", help="as for train (FastSpeech2.style_lengths; the training benchmark type)")
     sy = sub.add_parser("synthesize", help="Given some text and a trained model, write predicted spectrograms (reference fs2/cli/synthesize.py)")
     sy.add_argument("model_path", type=Path, help="a trained text-to-spec checkpoint")
     sy.add_argument("-t", "--text", dest="texts", action="append", default=[], help="some text to synthesize; can be repeated")
@@ -236,6 +243,16 @@ def attn_prior_mode(args, config) -> dict:
     return {"attn_prior": "computed" if asked else "files"}
 
 
+def style_lengths_mode(args, config) -> dict:
+    """``--style-lengths`` resolved against the model: what ``FastSpeech2.style_lengths`` is set to and what a dry run
+    reports -- with a note when the flag was given to a model without the style encoder."""
+    asked = bool(getattr(args, "style_lengths", False))
+    if asked and not config.model.use_global_style_token_module:
+        return {"style_lengths": False, "style_lengths_note": "--style-lengths ignored: model.use_global_style_token_module "
+                                                              "is false (there is no style encoder)"}
+    return {"style_lengths": asked}
+
+
 def bucket_count(args) -> Optional[int]:
     """``--bucket-lengths [N]``: None = off, otherwise the number of buckets (no value: the launch-plan limit).  More
     buckets than plans are allowed but warned about once: the limit is not raised (a plan's pool is gigabytes)."""
@@ -314,6 +331,7 @@ class Trainer:
         self._tiles_shared = world == 1
         self.n_buckets = bucket_count(args)
         cfg = self.model.config
+        self.model.style_lengths = style_lengths_mode(args, cfg)["style_lengths"]
         prior = attn_prior_mode(args, cfg)["attn_prior"]
         self.train_set = FeatureDataset(p["train_rows"], cfg, self.model.lang2id, self.model.speaker2id, attn_prior=prior)
         self.val_set = FeatureDataset(p["val_rows"], cfg, self.model.lang2id, self.model.speaker2id, attn_prior=prior)
@@ -400,6 +418,7 @@ class Trainer:
         rec["training/total_loss"] = float(slots[len(LOSS_KEYS)])
         r = self.opt.record()
         rec.update(lr=r["lr"], grad_norm=r["grad_norm"])
+        rec["style_lengths"] = bool(self.model.style_lengths)
         rec.update(self.model.plans.counters())  # steps replayed from / recorded into a launch plan, or run eagerly
         self.log(rec)
 
@@ -599,7 +618,7 @@ def train(args, argv) -> int:
             "lang2id": p["lang2id"], "speaker2id": p["speaker2id"], "batch_size": p["config"].training.batch_size,
             "max_steps": p["max_steps"], "max_epochs": p["max_epochs"], "monitor": MONITOR,
             "gradient_clip_val": GRADIENT_CLIP_VAL, "learn_alignment": p["config"].model.learn_alignment,
-            **attn_prior_mode(args, p["config"]),
+            **attn_prior_mode(args, p["config"]), **style_lengths_mode(args, p["config"]),
             "stats": sorted(p["stats"])}))
         return 0
     world = int(os.environ.get("WORLD_SIZE", 0))
@@ -654,6 +673,7 @@ def benchmark(args) -> int:
     config = p["config"]
     model = FastSpeech2(config, Stats(**p["stats"]), p["lang2id"], p["speaker2id"], precision=args.precision)
     model.eval()
+    model.style_lengths = style_lengths_mode(args, config)["style_lengths"]
     ds = FeatureDataset(p["train_rows"], config, p["lang2id"], p["speaker2id"],
                         attn_prior=attn_prior_mode(args, config)["attn_prior"])
     n = min(config.training.batch_size, len(ds))

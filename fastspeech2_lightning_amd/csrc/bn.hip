@@ -11,6 +11,7 @@
 //   apply      : out = dropout(act(y*scale + shift))                         (one pass)
 //   backward   : reduce (sum dz, sum dz*xhat) -> finalize (dgamma, dbeta, means) -> apply
 // The statistics passes sweep whole rows (contiguous >= 1 KiB per wavefront instruction).
+// The *_lens kernels are the same passes over the valid positions of a [B][H][W][C] tensor only (lengths in device memory).
 #include "common.h"
 #include "dispatch.h"
 
@@ -220,6 +221,11 @@ __device__ __forceinline__ float dz_of(float dout, float v, float sc, float sh, 
   return dout * fs2_drop_factor(drop, idx) * fs2_dact(act, fmaf(v, sc, sh));
 }
 
+// (without dropout: the same value, the factor being exactly 1)
+__device__ __forceinline__ float dz_of(float dout, float v, float sc, float sh, int act) {
+  return dout * fs2_dact(act, fmaf(v, sc, sh));
+}
+
 // dz = dout * dropmask * act'(y*scale+shift) ; partial[blk][0][C] = sum dz, [1] = sum dz * xhat
 template <bool IB, bool DB>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const void* __restrict__ dout, const void* __restrict__ y,
@@ -365,10 +371,262 @@ __global__ __launch_bounds__(64) void bn_bwd_small_kernel(const float* __restric
   }
 }
 
+// ---- BatchNorm over the VALID positions of y [B][H][W][C] only (length-aware training of the GST style encoder) ----
+// Utterance b keeps its first L = clamp(lens[b], 0, H) rows of H: seen as a [B * H * W][C] matrix, ONE contiguous range
+// of L * W rows starting at row b * H * W.  Every utterance's H * W rows are tiled in stripes of `pr` rows (ppu stripes
+// per utterance, part index b * ppu + p); a stripe's row count min(pr, L * W - p * pr) -- possibly 0 -- and the total
+// count come from lens in device memory, and no row at or beyond L * W is ever addressed.  The arithmetic is that of
+// the kernels above: pivot-shifted per-stripe sums, Chan merge in fp64.
+struct LensMap {
+  int H, W, HW, pr, ppu;
+};
+__device__ __forceinline__ int lens_valid_rows(const int* __restrict__ lens, int b, const LensMap& lm) {
+  const int l = lens[b];
+  return (l < 0 ? 0 : (l > lm.H ? lm.H : l)) * lm.W;
+}
+__device__ __forceinline__ long long lens_count(const int* __restrict__ lens, int B, const LensMap& lm) {
+  long long n = 0;
+  for (int b = 0; b < B; ++b) n += lens_valid_rows(lens, b, lm);
+  return n;
+}
+
+__global__ __launch_bounds__(256) void colstats_lens_kernel(const float* __restrict__ y, const int* __restrict__ lens,
+                                                             int C, float* __restrict__ partial, WideMap wm, LensMap lm) {
+  __shared__ float4 red[2][256];
+  const int tid = threadIdx.x;
+  const int rl = tid / wm.tpr, c4 = tid - rl * wm.tpr;
+  const int b = blockIdx.x / lm.ppu, p = blockIdx.x - b * lm.ppu;
+  const int nv = lens_valid_rows(lens, b, lm);
+  const int r0 = p * lm.pr, r1 = min(nv, r0 + lm.pr);
+  if (r1 <= r0) {  // (uniform over the workgroup) an empty stripe: count 0, never read
+    if (rl == 0) {
+      *reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 0) * C + c4 * 4) = make_float4(0, 0, 0, 0);
+      *reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 1) * C + c4 * 4) = make_float4(0, 0, 0, 0);
+    }
+    return;
+  }
+  const float* yb = y + (long long)b * lm.HW * C;
+  float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0), pv = make_float4(0, 0, 0, 0);
+  if (rl < wm.rpi) {
+    pv = *reinterpret_cast<const float4*>(yb + (long long)r0 * C + c4 * 4);
+    for (int r = r0 + rl; r < r1; r += wm.rpi) {
+      float4 v = *reinterpret_cast<const float4*>(yb + (long long)r * C + c4 * 4);
+      v.x -= pv.x; v.y -= pv.y; v.z -= pv.z; v.w -= pv.w;
+      s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
+      s2.x += v.x * v.x; s2.y += v.y * v.y; s2.z += v.z * v.z; s2.w += v.w * v.w;
+    }
+  }
+  red[0][tid] = s1;
+  red[1][tid] = s2;
+  __syncthreads();
+  if (rl == 0) {
+    for (int l = 1; l < wm.rpi; ++l) {
+      float4 a = red[0][l * wm.tpr + c4], e = red[1][l * wm.tpr + c4];
+      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
+      s2.x += e.x; s2.y += e.y; s2.z += e.z; s2.w += e.w;
+    }
+    const float inv = 1.f / (float)(r1 - r0);
+    float4 mean, m2;
+    mean.x = pv.x + s1.x * inv; m2.x = fmaxf(s2.x - s1.x * s1.x * inv, 0.f);
+    mean.y = pv.y + s1.y * inv; m2.y = fmaxf(s2.y - s1.y * s1.y * inv, 0.f);
+    mean.z = pv.z + s1.z * inv; m2.z = fmaxf(s2.z - s1.z * s1.z * inv, 0.f);
+    mean.w = pv.w + s1.w * inv; m2.w = fmaxf(s2.w - s1.w * s1.w * inv, 0.f);
+    *reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 0) * C + c4 * 4) = mean;
+    *reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 1) * C + c4 * 4) = m2;
+  }
+}
+
+// bn_finalize_kernel's training branch with the stripes' counts and the total count N taken from lens.  N = 0 (no
+// valid position at all): mean 0, variance 0, running buffers untouched.
+__global__ __launch_bounds__(1024) void bn_finalize_lens_kernel(const float* __restrict__ partial,
+                                                                 const int* __restrict__ lens, int B,
+                                                                 const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, float* __restrict__ rmean,
+                                                                 float* __restrict__ rvar, float momentum, float eps,
+                                                                 float* __restrict__ stats, int C, LensMap lm) {
+  __shared__ double red[16][FIN_CH];
+  const int c = blockIdx.x * FIN_CH + (threadIdx.x & 15);
+  const bool writer = threadIdx.x < FIN_CH && c < C;
+  const long long count = lens_count(lens, B, lm);
+  const int nparts = B * lm.ppu;
+  auto cnt = [&](int p) {
+    const int b = p / lm.ppu;
+    return (double)max(0, min(lm.pr, lens_valid_rows(lens, b, lm) - (p - b * lm.ppu) * lm.pr));
+  };
+  double a, e;
+  fin_parts(partial, nparts, C, c, [&](int p, float u, float, double& x, double&) { x += cnt(p) * (double)u; }, a, e);
+  const double sum = fin_sum(a, red);
+  const double mu = count > 0 ? sum / (double)count : 0.0;
+  fin_parts(partial, nparts, C, c, [&](int p, float u, float v, double& x, double&) {
+    const double d = (double)u - mu;
+    x += (double)v + cnt(p) * d * d;
+  }, a, e);
+  const double m2 = fin_sum(a, red);
+  if (!writer) return;
+  double var = count > 0 ? m2 / (double)count : 0.0;
+  if (var < 0.0) var = 0.0;
+  const float mean = (float)mu, invstd = (float)(1.0 / sqrt(var + (double)eps));
+  if (rmean && count > 0) {
+    double unbiased = count > 1 ? var * (double)count / (double)(count - 1) : var;
+    rmean[c] = (1.f - momentum) * rmean[c] + momentum * mean;
+    rvar[c] = (1.f - momentum) * rvar[c] + momentum * (float)unbiased;
+  }
+  const float sc = gamma[c] * invstd;
+  stats[0 * C + c] = sc;
+  stats[1 * C + c] = beta[c] - mean * sc;
+  stats[2 * C + c] = mean;
+  stats[3 * C + c] = invstd;
+  stats[4 * C + c] = eps;
+}
+
+// bn_bwd_reduce_kernel over the valid rows of a stripe (no dropout): partial[part][0][C] = sum dz, [1] = sum dz * xhat
+__global__ __launch_bounds__(256) void bn_bwd_reduce_lens_kernel(const float* __restrict__ dout, const float* __restrict__ y,
+                                                                  const float* __restrict__ stats,
+                                                                  const int* __restrict__ lens, int C, int act,
+                                                                  float* __restrict__ partial, WideMap wm, LensMap lm) {
+  __shared__ float4 red[2][256];
+  const int tid = threadIdx.x;
+  const int rl = tid / wm.tpr, c4 = tid - rl * wm.tpr;
+  const int b = blockIdx.x / lm.ppu, p = blockIdx.x - b * lm.ppu;
+  const int nv = lens_valid_rows(lens, b, lm);
+  const int r0 = p * lm.pr, r1 = min(nv, r0 + lm.pr);
+  float4 s1 = make_float4(0, 0, 0, 0), s2 = make_float4(0, 0, 0, 0);
+  if (rl < wm.rpi && r0 < r1) {
+    const float4 sc = reinterpret_cast<const float4*>(stats)[c4], sh = reinterpret_cast<const float4*>(stats + C)[c4];
+    const float4 mu = reinterpret_cast<const float4*>(stats + 2 * C)[c4], is = reinterpret_cast<const float4*>(stats + 3 * C)[c4];
+    for (int r = r0 + rl; r < r1; r += wm.rpi) {
+      const long long idx = ((long long)b * lm.HW + r) * C + c4 * 4;
+      const float4 v = *reinterpret_cast<const float4*>(y + idx), d = *reinterpret_cast<const float4*>(dout + idx);
+      float dz;
+      dz = dz_of(d.x, v.x, sc.x, sh.x, act); s1.x += dz; s2.x += dz * (v.x - mu.x) * is.x;
+      dz = dz_of(d.y, v.y, sc.y, sh.y, act); s1.y += dz; s2.y += dz * (v.y - mu.y) * is.y;
+      dz = dz_of(d.z, v.z, sc.z, sh.z, act); s1.z += dz; s2.z += dz * (v.z - mu.z) * is.z;
+      dz = dz_of(d.w, v.w, sc.w, sh.w, act); s1.w += dz; s2.w += dz * (v.w - mu.w) * is.w;
+    }
+  }
+  red[0][tid] = s1;
+  red[1][tid] = s2;
+  __syncthreads();
+  if (rl == 0) {
+    for (int l = 1; l < wm.rpi; ++l) {
+      float4 a = red[0][l * wm.tpr + c4], e = red[1][l * wm.tpr + c4];
+      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
+      s2.x += e.x; s2.y += e.y; s2.z += e.z; s2.w += e.w;
+    }
+    *reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 0) * C + c4 * 4) = s1;
+    *reinterpret_cast<float4*>(partial + ((long long)blockIdx.x * 2 + 1) * C + c4 * 4) = s2;
+  }
+}
+
+// bn_bwd_finalize_kernel with the count N taken from lens (N = 0: the sums are 0 and so are the means)
+__global__ __launch_bounds__(1024) void bn_bwd_finalize_lens_kernel(const float* __restrict__ partial,
+                                                                     const int* __restrict__ lens, int B,
+                                                                     float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                     float* __restrict__ coef, int C, LensMap lm) {
+  __shared__ double red[16][FIN_CH];
+  const int c = blockIdx.x * FIN_CH + (threadIdx.x & 15);
+  const long long count = lens_count(lens, B, lm);
+  double a, e;
+  fin_parts(partial, B * lm.ppu, C, c, [&](int, float u, float v, double& x, double& y) { x += (double)u; y += (double)v; }, a, e);
+  const double s1 = fin_sum(a, red), s2 = fin_sum(e, red);
+  if (threadIdx.x >= FIN_CH || c >= C) return;
+  dbeta[c] = (float)s1;
+  dgamma[c] = (float)s2;
+  const double n = count > 0 ? (double)count : 1.0;
+  coef[c] = (float)(s1 / n);
+  coef[C + c] = (float)(s2 / n);
+}
+
+// The training-mode backward of FEW valid rows in fp64, one thread per channel: bn_bwd_small_kernel (see there for why)
+// over the valid rows.  Returns at once when there are more than BN_SMALL_ROWS of them, or none.
+__global__ __launch_bounds__(64) void bn_bwd_small_lens_kernel(const float* __restrict__ dout, const float* __restrict__ y,
+                                                                const float* __restrict__ stats,
+                                                                const int* __restrict__ lens, int B,
+                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                float* __restrict__ dy, int C, int act, LensMap lm) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= C) return;
+  const long long M = lens_count(lens, B, lm);
+  if (M > BN_SMALL_ROWS || M == 0) return;
+  const float sc = stats[c], sh = stats[C + c];
+  const double eps = (double)stats[4 * C + c];
+  auto rows = [&](auto&& f) {
+    for (int b = 0; b < B; ++b) {
+      const int nv = lens_valid_rows(lens, b, lm);
+      for (int r = 0; r < nv; ++r) f(((long long)b * lm.HW + r) * C + c);
+    }
+  };
+  double mu = 0.0, m2 = 0.0;
+  rows([&](long long idx) { mu += (double)y[idx]; });
+  mu /= (double)M;
+  rows([&](long long idx) {
+    const double d = (double)y[idx] - mu;
+    m2 += d * d;
+  });
+  const double invstd = 1.0 / sqrt(m2 / (double)M + eps);
+  double s1 = 0.0, s2 = 0.0;
+  rows([&](long long idx) {
+    const double dz = (double)dz_of(dout[idx], y[idx], sc, sh, act);
+    s1 += dz;
+    s2 += dz * (((double)y[idx] - mu) * invstd);
+  });
+  dbeta[c] = (float)s1;
+  dgamma[c] = (float)s2;
+  const double k1 = s1 / (double)M, k2 = s2 / (double)M;
+  rows([&](long long idx) {
+    const double dz = (double)dz_of(dout[idx], y[idx], sc, sh, act);
+    dy[idx] = (float)((double)sc * (dz - k1 - ((double)y[idx] - mu) * invstd * k2));
+  });
+}
+
+// dy = scale * (dz - mean(dz) - xhat * mean(dz * xhat)) on the valid rows, 0 on the others (whose dout and y are never
+// read).  With N <= BN_SMALL_ROWS valid rows the valid rows are bn_bwd_small_lens_kernel's and are left alone here.
+__global__ __launch_bounds__(256) void bn_bwd_apply_lens_kernel(const float* __restrict__ dout, const float* __restrict__ y,
+                                                                 const float* __restrict__ stats,
+                                                                 const float* __restrict__ coef,
+                                                                 const int* __restrict__ lens, int B,
+                                                                 float* __restrict__ dy, long long n4, int C, int act,
+                                                                 LensMap lm) {
+  const int c4n = C >> 2;
+  const long long count = lens_count(lens, B, lm);
+  const bool small = count > 0 && count <= BN_SMALL_ROWS;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long long)gridDim.x * blockDim.x) {
+    const long long row = i / c4n;
+    const int c4 = (int)(i - row * c4n);
+    const int b = (int)(row / lm.HW);
+    if ((int)(row - (long long)b * lm.HW) >= lens_valid_rows(lens, b, lm)) {
+      reinterpret_cast<float4*>(dy)[i] = make_float4(0, 0, 0, 0);
+      continue;
+    }
+    if (small) continue;
+    const float4 sc = reinterpret_cast<const float4*>(stats)[c4], sh = reinterpret_cast<const float4*>(stats + C)[c4];
+    const float4 v = reinterpret_cast<const float4*>(y)[i], d = reinterpret_cast<const float4*>(dout)[i];
+    const float4 mu = reinterpret_cast<const float4*>(stats + 2 * C)[c4], is = reinterpret_cast<const float4*>(stats + 3 * C)[c4];
+    const float4 k1 = reinterpret_cast<const float4*>(coef)[c4], k2 = reinterpret_cast<const float4*>(coef + C)[c4];
+    float4 dz;
+    dz.x = dz_of(d.x, v.x, sc.x, sh.x, act) - k1.x - (v.x - mu.x) * is.x * k2.x;
+    dz.y = dz_of(d.y, v.y, sc.y, sh.y, act) - k1.y - (v.y - mu.y) * is.y * k2.y;
+    dz.z = dz_of(d.z, v.z, sc.z, sh.z, act) - k1.z - (v.z - mu.z) * is.z * k2.z;
+    dz.w = dz_of(d.w, v.w, sc.w, sh.w, act) - k1.w - (v.w - mu.w) * is.w * k2.w;
+    reinterpret_cast<float4*>(dy)[i] = make_float4(sc.x * dz.x, sc.y * dz.y, sc.z * dz.z, sc.w * dz.w);
+  }
+}
+
 bool wide_ok(int C, WideMap& wm) {
   if ((C % 4) || C > 1024) return false;
   wm.tpr = C / 4;
   wm.rpi = 256 / wm.tpr;
+  return true;
+}
+
+// the stripes of the length-aware kernels: as tall as colstats takes them for the whole [B * H * W][C] matrix
+bool lens_map(int B, int H, int W, LensMap& lm) {
+  if (B <= 0 || H <= 0 || W <= 0 || (long long)B * H * W > 0x7fffffffLL) return false;
+  lm.H = H;
+  lm.W = W;
+  lm.HW = H * W;
+  lm.pr = cs_rows(B * lm.HW);
+  lm.ppu = (lm.HW + lm.pr - 1) / lm.pr;
   return true;
 }
 
@@ -482,4 +740,53 @@ extern "C" int fs2hip_bn_act_bwd_b(const void* dout, const void* y, const float*
       return fs2_launched();
     });
   });
+}
+
+// ---- BatchNorm over the valid positions only (the kernels above; include/fs2hip.h) ----
+extern "C" int fs2hip_bn_lens_parts(int B, int H, int W) {
+  LensMap lm;
+  return lens_map(B, H, W, lm) ? B * lm.ppu : 0;
+}
+
+// partial: [fs2hip_bn_lens_parts(B, H, W)][2][C] scratch (16-byte aligned)
+extern "C" int fs2hip_bn_stats_lens(const float* y, const int* lens, float* partial, const float* gamma, const float* beta,
+                                    float* running_mean, float* running_var, float momentum, float eps, float* stats,
+                                    int B, int H, int W, int C, void* stream) {
+  WideMap wm;
+  LensMap lm;
+  if (!y || !lens || !partial || !gamma || !beta || !stats || !lens_map(B, H, W, lm) || C <= 0 || !wide_ok(C, wm) ||
+      (!running_mean != !running_var) || ((uintptr_t)y % 16) || ((uintptr_t)partial % 16))
+    return FS2HIP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  colstats_lens_kernel<<<dim3(B * lm.ppu), dim3(256), 0, s>>>(y, lens, C, partial, wm, lm);
+  FS2_LAUNCH_CHECK();
+  bn_finalize_lens_kernel<<<dim3((C + FIN_CH - 1) / FIN_CH), dim3(1024), 0, s>>>(partial, lens, B, gamma, beta, running_mean,
+                                                                              running_var, momentum, eps, stats, C, lm);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+// partial as above; coef: [2][C] scratch (16-byte aligned)
+extern "C" int fs2hip_bn_act_bwd_lens(const float* dout, const float* y, const float* stats, const int* lens, float* partial,
+                                      float* coef, float* dgamma, float* dbeta, float* dy, int B, int H, int W, int C,
+                                      int act, void* stream) {
+  WideMap wm;
+  LensMap lm;
+  if (!dout || !y || !stats || !lens || !partial || !coef || !dgamma || !dbeta || !dy || !lens_map(B, H, W, lm) || C <= 0 ||
+      !wide_ok(C, wm) || ((uintptr_t)dout % 16) || ((uintptr_t)y % 16) || ((uintptr_t)stats % 16) ||
+      ((uintptr_t)partial % 16) || ((uintptr_t)coef % 16) || ((uintptr_t)dy % 16))
+    return FS2HIP_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  bn_bwd_reduce_lens_kernel<<<dim3(B * lm.ppu), dim3(256), 0, s>>>(dout, y, stats, lens, C, act, partial, wm, lm);
+  FS2_LAUNCH_CHECK();
+  bn_bwd_finalize_lens_kernel<<<dim3((C + FIN_CH - 1) / FIN_CH), dim3(1024), 0, s>>>(partial, lens, B, dgamma, dbeta, coef, C, lm);
+  FS2_LAUNCH_CHECK();
+  const long long n4 = (long long)B * lm.HW * C / 4;
+  long long blocks = (n4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  bn_bwd_apply_lens_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(dout, y, stats, coef, lens, B, dy, n4, C, act, lm);
+  FS2_LAUNCH_CHECK();
+  bn_bwd_small_lens_kernel<<<dim3((C + 63) / 64), dim3(64), 0, s>>>(dout, y, stats, lens, B, dgamma, dbeta, dy, C, act, lm);
+  FS2_LAUNCH_CHECK();
+  return 0;
 }

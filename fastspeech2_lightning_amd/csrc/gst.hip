@@ -6,6 +6,8 @@
 //   gst_attn        : softmax(q k^T / sqrt(d_k)) v of one query per utterance against the style tokens
 //   gru_last_state  : the whole inference recurrence in one launch, a step count per utterance (length-aware inference)
 //   conv_s2_lens    : the row counts an utterance keeps after each stride-2 convolution
+//   gru_fwd_states  : gru_last_state kept for training: also writes every step's state and gates (168 VGPRs, no scratch)
+//   gru_bwd_states  : the whole backward through time in one launch, w_hh columns in registers (152 VGPRs, no scratch)
 #include "common.h"
 
 namespace {
@@ -307,6 +309,147 @@ __global__ __launch_bounds__(3 * GRU_U) void gru_last_state_kernel(const float* 
   if (j < U) h_out[(long long)b * U + j] = h;
 }
 
+// ---- the same recurrence kept for training (fs2hip_gru_fwd_states): gru_last_state_kernel, step for step and in its
+// arithmetic order (the final state is bit-equal), which also writes hs [B][T+1][U] (hs[b][0] = 0, hs[b][t+1] = the state
+// after step t) and gates [B][T][4U] = (r, z, n, gh_n) as gru_gate_fwd_kernel saves them.  Rows beyond the utterance's
+// step count are written as zeros: a weight-gradient GEMM over all rows multiplies them by zero gradient rows.
+__global__ __launch_bounds__(3 * GRU_U) void gru_fwd_states_kernel(const float* __restrict__ gi,
+                                                                    const float* __restrict__ w_hh,
+                                                                    const float* __restrict__ b_hh,
+                                                                    const int* __restrict__ steps, float* __restrict__ hs,
+                                                                    float* __restrict__ gates, float* __restrict__ h_out,
+                                                                    int T) {
+  constexpr int U = GRU_U;
+  __shared__ __attribute__((aligned(16))) float sh[U];
+  __shared__ float sgh[3 * U];
+  const int b = blockIdx.x, j = threadIdx.x;
+  int n = steps[b];
+  n = n < 0 ? 0 : (n > T ? T : n);
+  float* hsb = hs + (long long)b * (T + 1) * U;
+  float* gtb = gates + (long long)b * T * 4 * U;
+  // the rows no step writes: hs[b][0], hs[b][n + 1 ..], gates[b][n ..]
+  for (int i = j; i < (T + 1) * U; i += 3 * U)
+    if (i < U || i >= (n + 1) * U) hsb[i] = 0.f;
+  for (int i = n * 4 * U + j; i < T * 4 * U; i += 3 * U) gtb[i] = 0.f;
+  if (n == 0) {  // (uniform over the workgroup)
+    if (j < U) h_out[(long long)b * U + j] = 0.f;
+    return;
+  }
+  float w[U];
+  const f32x4* wrow = reinterpret_cast<const f32x4*>(w_hh + (long long)j * U);
+#pragma unroll
+  for (int k4 = 0; k4 < U / 4; ++k4) {
+    const f32x4 v = wrow[k4];
+    w[4 * k4] = v[0]; w[4 * k4 + 1] = v[1]; w[4 * k4 + 2] = v[2]; w[4 * k4 + 3] = v[3];
+  }
+  const float bias = b_hh[j];
+  float h = 0.f;  // thread j < U: element j of the state
+  if (j < U) sh[j] = 0.f;
+  __syncthreads();
+  const float* gib = gi + (long long)b * T * 3 * U;
+  const f32x4* sh4 = reinterpret_cast<const f32x4*>(sh);
+  for (int t = 0; t < n; ++t) {
+    float gr = 0.f, gz = 0.f, gn = 0.f;
+    if (j < U) {
+      const float* g = gib + (long long)t * 3 * U;
+      gr = g[j]; gz = g[U + j]; gn = g[2 * U + j];
+    }
+    float acc = 0.f;
+#pragma unroll
+    for (int k4 = 0; k4 < U / 4; ++k4) {
+      const f32x4 hv = sh4[k4];
+      acc = fmaf(hv[0], w[4 * k4], acc);
+      acc = fmaf(hv[1], w[4 * k4 + 1], acc);
+      acc = fmaf(hv[2], w[4 * k4 + 2], acc);
+      acc = fmaf(hv[3], w[4 * k4 + 3], acc);
+    }
+    sgh[j] = acc + bias;
+    __syncthreads();
+    if (j < U) {
+      const float hn = sgh[2 * U + j];
+      const float r = fs2_sigmoid(gr + sgh[j]);
+      const float z = fs2_sigmoid(gz + sgh[U + j]);
+      const float c = tanhf(gn + r * hn);
+      h = (1.f - z) * c + z * h;
+      sh[j] = h;
+      float* g = gtb + (long long)t * 4 * U;
+      g[j] = r; g[U + j] = z; g[2 * U + j] = c; g[3 * U + j] = hn;
+      hsb[(long long)(t + 1) * U + j] = h;
+    }
+    __syncthreads();
+  }
+  if (j < U) h_out[(long long)b * U + j] = h;
+}
+
+// ---- the whole backward through time in one launch (fs2hip_gru_bwd_states), one workgroup per utterance ----
+// Thread (g, k) = threadIdx g * U + k keeps COLUMN k of gate block g of w_hh [3U][U] in 128 registers (strided loads,
+// coalesced over k, once).  A step, from the utterance's last down to 0: the first U threads take the gate derivatives
+// of gru_gate_bwd_kernel from dh (a register), the saved gates and h_{t-1}, write dgi[b][t] and dgh[b][t] and leave dgh in
+// LDS; a barrier; every thread's dot product of its column with its gate block's dgh (broadcast LDS reads, i ascending,
+// one fmaf chain); a barrier; dh_{t-1}[k] = dh[k] * z[k] + ((part_r[k] + part_z[k]) + part_n[k]).  Rows at and beyond
+// the step count -- row T of dgh included, which pairs with hs[b][T] in the recurrent weight gradient -- are exact zeros.
+// Nothing is read from another utterance: a row's outputs are bit-equal whatever the batch.
+__global__ __launch_bounds__(3 * GRU_U) void gru_bwd_states_kernel(const float* __restrict__ dh_last,
+                                                                    const float* __restrict__ hs,
+                                                                    const float* __restrict__ gates,
+                                                                    const float* __restrict__ w_hh,
+                                                                    const int* __restrict__ steps, float* __restrict__ dgi,
+                                                                    float* __restrict__ dgh, float* __restrict__ dh0,
+                                                                    int T) {
+  constexpr int U = GRU_U;
+  __shared__ __attribute__((aligned(16))) float sd[3 * U];
+  __shared__ float sp[3 * U];
+  const int b = blockIdx.x, j = threadIdx.x;
+  int n = steps[b];
+  n = n < 0 ? 0 : (n > T ? T : n);
+  float* dgib = dgi + (long long)b * T * 3 * U;
+  float* dghb = dgh + (long long)b * (T + 1) * 3 * U;
+  for (int i = n * 3 * U + j; i < T * 3 * U; i += 3 * U) dgib[i] = 0.f;
+  for (int i = n * 3 * U + j; i < (T + 1) * 3 * U; i += 3 * U) dghb[i] = 0.f;
+  float d = j < U ? dh_last[(long long)b * U + j] : 0.f;
+  if (n == 0) {  // (uniform over the workgroup) no step: h_last = h0
+    if (j < U) dh0[(long long)b * U + j] = d;
+    return;
+  }
+  const int gb = j / U, k = j - gb * U;
+  float w[U];
+#pragma unroll
+  for (int i = 0; i < U; ++i) w[i] = w_hh[(long long)(gb * U + i) * U + k];
+  const float* hsb = hs + (long long)b * (T + 1) * U;
+  const float* gtb = gates + (long long)b * T * 4 * U;
+  const f32x4* sd4 = reinterpret_cast<const f32x4*>(sd + gb * U);
+  for (int t = n - 1; t >= 0; --t) {
+    float z = 0.f;
+    if (j < U) {
+      const float* g = gtb + (long long)t * 4 * U;
+      const float r = g[j], c = g[2 * U + j], hn = g[3 * U + j];
+      z = g[U + j];
+      const float dn = d * (1.f - z) * (1.f - c * c);
+      const float dz = d * (hsb[(long long)t * U + j] - c) * z * (1.f - z);
+      const float dr = dn * hn * r * (1.f - r);
+      float* a = dgib + (long long)t * 3 * U;
+      float* e = dghb + (long long)t * 3 * U;
+      a[j] = dr; a[U + j] = dz; a[2 * U + j] = dn;
+      e[j] = dr; e[U + j] = dz; e[2 * U + j] = dn * r;
+      sd[j] = dr; sd[U + j] = dz; sd[2 * U + j] = dn * r;
+    }
+    __syncthreads();
+    float acc = 0.f;
+#pragma unroll
+    for (int i4 = 0; i4 < U / 4; ++i4) {
+      const f32x4 v = sd4[i4];
+      acc = fmaf(v[0], w[4 * i4], acc);
+      acc = fmaf(v[1], w[4 * i4 + 1], acc);
+      acc = fmaf(v[2], w[4 * i4 + 2], acc);
+      acc = fmaf(v[3], w[4 * i4 + 3], acc);
+    }
+    sp[j] = acc;
+    __syncthreads();
+    if (j < U) d = d * z + ((sp[j] + sp[U + j]) + sp[2 * U + j]);
+  }
+  if (j < U) dh0[(long long)b * U + j] = d;
+}
+
 // table[l][b], l = 0 .. n: the row counts an utterance of lens[b] frames has after l stride-2 convolutions
 __global__ void conv_s2_lens_kernel(const int* __restrict__ lens, int* __restrict__ table, int B, int n) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -471,6 +614,26 @@ extern "C" int fs2hip_gru_last_state(const float* gi, const float* w_hh, const f
   if (!gi || !w_hh || !b_hh || !steps || !h_out || B <= 0 || T <= 0 || U != GRU_U || ((uintptr_t)w_hh % 16))
     return FS2HIP_EINVAL;
   gru_last_state_kernel<<<dim3(B), dim3(3 * GRU_U), 0, S_>>>(gi, w_hh, b_hh, steps, h_out, T);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_gru_fwd_states(const float* gi, const float* w_hh, const float* b_hh, const int* steps, float* hs,
+                                     float* gates, float* h_out, int B, int T, int U, void* stream) {
+  if (!gi || !w_hh || !b_hh || !steps || !hs || !gates || !h_out || B <= 0 || T <= 0 || U != GRU_U ||
+      ((uintptr_t)w_hh % 16))
+    return FS2HIP_EINVAL;
+  gru_fwd_states_kernel<<<dim3(B), dim3(3 * GRU_U), 0, S_>>>(gi, w_hh, b_hh, steps, hs, gates, h_out, T);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_gru_bwd_states(const float* dh_last, const float* hs, const float* gates, const float* w_hh,
+                                     const int* steps, float* dgi, float* dgh, float* dh0, int B, int T, int U,
+                                     void* stream) {
+  if (!dh_last || !hs || !gates || !w_hh || !steps || !dgi || !dgh || !dh0 || B <= 0 || T <= 0 || U != GRU_U)
+    return FS2HIP_EINVAL;
+  gru_bwd_states_kernel<<<dim3(B), dim3(3 * GRU_U), 0, S_>>>(dh_last, hs, gates, w_hh, steps, dgi, dgh, dh0, T);
   FS2_LAUNCH_CHECK();
   return 0;
 }

@@ -156,6 +156,11 @@ SIGNATURES = {
     "fs2hip_pack_rows": None,  # (const Fs2PackMember*, int, int, void*): set below
     "fs2hip_gru_last_state": "pppppiiip",
     "fs2hip_conv_s2_lens": "ppiip",
+    "fs2hip_gru_fwd_states": "pppppppiiip",
+    "fs2hip_gru_bwd_states": "ppppppppiiip",
+    "fs2hip_bn_lens_parts": "iii",
+    "fs2hip_bn_stats_lens": "pppppppffpiiiip",
+    "fs2hip_bn_act_bwd_lens": "pppppppppiiiiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -2464,6 +2469,105 @@ def conv_s2_lens(lens, n):
     table = torch.empty(n + 1, lens.numel(), device=lens.device, dtype=torch.int32)
     _ok(lib().fs2hip_conv_s2_lens(_p(lens), _p(table), lens.numel(), n, _stream()), "conv_s2_lens")
     return table
+
+
+def _gru_shapes(fn, w_hh, B, T, steps):
+    U = w_hh.shape[-1]
+    _req(U == 128, f"{fn}: U = {U}, only 128 (the reference encoder's GRU) is built")
+    _req(w_hh.shape == (3 * U, U), f"{fn}: w_hh {tuple(w_hh.shape)} does not fit U = {U}")
+    _req(B > 0 and T > 0, f"{fn}: B = {B}, T = {T} (at least 1)")
+    _req(steps.numel() == B, f"{fn}: steps has {steps.numel()} entries for {B} utterances")
+    return U
+
+
+def gru_fwd_states(gi, w_hh, b_hh, steps):
+    """``gru_last_state`` kept for training, in ONE launch: returns ``(h_last [B, U], hs [B, T + 1, U], gates [B, T, 4U])``
+    -- ``h_last`` bit-equal to ``gru_last_state``'s, ``hs[b, 0] = 0`` and ``hs[b, t + 1]`` the state after step t, ``gates``
+    = (r, z, n, gh_n) per step.  Rows of ``gi`` at and beyond ``clamp(steps[b], 0, T)`` are never read; the rows of ``hs``
+    and ``gates`` beyond it are zeros.  U = 128 only."""
+    _chk(gi, name="gi"); _chk(w_hh, name="w_hh"); _chk(b_hh, name="b_hh"); _chk(steps, torch.int32, "steps")
+    _req(gi.dim() == 3 and gi.numel() > 0, f"gru_fwd_states: gi must be a non-empty [B, T, 3U], got {tuple(gi.shape)}")
+    B, T, G = gi.shape
+    U = _gru_shapes("gru_fwd_states", w_hh, B, T, steps)
+    _req(b_hh.shape == (3 * U,) and G == 3 * U,
+         f"gru_fwd_states: gi {tuple(gi.shape)}, b_hh {tuple(b_hh.shape)} do not fit U = {U}")
+    _req(w_hh.data_ptr() % 16 == 0, "gru_fwd_states: w_hh must be 16-byte aligned")
+    h = torch.empty(B, U, device=gi.device, dtype=torch.float32)
+    hs = torch.empty(B, T + 1, U, device=gi.device, dtype=torch.float32)
+    gates = torch.empty(B, T, 4 * U, device=gi.device, dtype=torch.float32)
+    _ok(lib().fs2hip_gru_fwd_states(_p(gi), _p(w_hh), _p(b_hh), _p(steps), _p(hs), _p(gates), _p(h), B, T, U, _stream()),
+        "gru_fwd_states")
+    return h, hs, gates
+
+
+def gru_bwd_states(dh_last, hs, gates, w_hh, steps):
+    """The backward of ``gru_fwd_states`` through time in ONE launch: ``dh_last`` [B, U] -> ``(dgi [B, T, 3U], dgh
+    [B, T + 1, 3U], dh0 [B, U])``.  ``dgh[b, t]`` pairs with ``hs[b, t]`` (``dgh^T hs`` over all ``B * (T + 1)`` rows is
+    the gradient of ``w_hh``, the column sums that of ``b_hh``); rows at and beyond a row's step count, row T of ``dgh``
+    included, are exact zeros.  A row's results depend on that row alone."""
+    for n, t in (("dh_last", dh_last), ("hs", hs), ("gates", gates), ("w_hh", w_hh)):
+        _chk(t, name=n)
+    _chk(steps, torch.int32, "steps")
+    _req(gates.dim() == 3 and gates.numel() > 0, f"gru_bwd_states: gates must be a non-empty [B, T, 4U], got {tuple(gates.shape)}")
+    B, T, G = gates.shape
+    U = _gru_shapes("gru_bwd_states", w_hh, B, T, steps)
+    _req(G == 4 * U and tuple(hs.shape) == (B, T + 1, U) and tuple(dh_last.shape) == (B, U),
+         f"gru_bwd_states: gates {tuple(gates.shape)}, hs {tuple(hs.shape)}, dh_last {tuple(dh_last.shape)} do not fit "
+         f"U = {U}")
+    dgi = torch.empty(B, T, 3 * U, device=hs.device, dtype=torch.float32)
+    dgh = torch.empty(B, T + 1, 3 * U, device=hs.device, dtype=torch.float32)
+    dh0 = torch.empty(B, U, device=hs.device, dtype=torch.float32)
+    _ok(lib().fs2hip_gru_bwd_states(_p(dh_last), _p(hs), _p(gates), _p(w_hh), _p(steps), _p(dgi), _p(dgh), _p(dh0), B, T, U,
+                                    _stream()), "gru_bwd_states")
+    return dgi, dgh, dh0
+
+
+def _bn_lens_shapes(fn, y, lens):
+    _chk(y, name="y"); _chk(lens, torch.int32, "lens")
+    _req(y.dim() == 4 and y.numel() > 0, f"{fn}: y must be a non-empty [B, H, W, C], got {tuple(y.shape)}")
+    B, Hh, Ww, Cc = y.shape
+    _req(lens.numel() == B, f"{fn}: lens has {lens.numel()} entries for {B} utterances")
+    _req(Cc % 4 == 0 and Cc <= 1024, f"{fn}: C = {Cc} (a multiple of 4, at most 1024)")
+    parts = lib().fs2hip_bn_lens_parts(B, Hh, Ww)
+    _req(parts > 0, f"{fn}: y {tuple(y.shape)} is too large")
+    return B, Hh, Ww, Cc, parts
+
+
+def bn_stats_lens(y, lens, gamma, beta, running_mean=None, running_var=None, *, momentum=0.1, eps=1e-5):
+    """Training-mode BatchNorm statistics over the VALID positions of ``y`` [B, H, W, C] only -- utterance b keeps its first
+    ``clamp(lens[b], 0, H)`` rows of H; ``lens`` [B] int32 stays in GPU memory and rows beyond it are never read.  Returns
+    stats [5, C] as ``bn_finalize`` does (for ``bn_act_fwd``) and moves the running buffers with the unbiased variance
+    of the N = W * sum(L) valid positions."""
+    B, Hh, Ww, Cc, parts = _bn_lens_shapes("bn_stats_lens", y, lens)
+    _chk(gamma, name="gamma"); _chk(beta, name="beta")
+    _req(gamma.numel() == Cc and beta.numel() == Cc, "bn_stats_lens: gamma / beta size")
+    _req((running_mean is None) == (running_var is None), "bn_stats_lens: both running buffers or neither")
+    if running_mean is not None:
+        _chk(running_mean, name="running_mean"); _chk(running_var, name="running_var")
+        _req(running_mean.numel() == Cc and running_var.numel() == Cc, "bn_stats_lens: running stats size")
+    ws = reserve_workspace(parts * 2 * Cc)
+    stats = torch.empty(5, Cc, device=y.device, dtype=torch.float32)
+    _ok(lib().fs2hip_bn_stats_lens(_p(y), _p(lens), _p(ws), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                                   momentum, eps, _p(stats), B, Hh, Ww, Cc, _stream()), "bn_stats_lens")
+    return stats
+
+
+def bn_act_bwd_lens(dout, y, stats, lens, dgamma, dbeta, act=None):
+    """Backward of ``act(BatchNorm(y))`` with the statistics of ``bn_stats_lens``: writes ``dgamma`` / ``dbeta`` and returns
+    dy [B, H, W, C]; sums and 1 / N run over the valid positions, rows of dy beyond the lengths are zeros, rows of ``dout``
+    and ``y`` beyond them are never read."""
+    B, Hh, Ww, Cc, parts = _bn_lens_shapes("bn_act_bwd_lens", y, lens)
+    _chk(dout, name="dout")
+    for n, t in (("stats", stats), ("dgamma", dgamma), ("dbeta", dbeta)):
+        _chk(t, name=n)
+    _req(dout.shape == y.shape and stats.numel() == 5 * Cc and dgamma.numel() == Cc and dbeta.numel() == Cc,
+         "bn_act_bwd_lens: shape mismatch")
+    ws = reserve_workspace(parts * 2 * Cc + 2 * Cc)
+    coef_ptr = ws.data_ptr() + 4 * parts * 2 * Cc
+    dy = torch.empty(y.shape, device=y.device, dtype=torch.float32)
+    _ok(lib().fs2hip_bn_act_bwd_lens(_p(dout), _p(y), _p(stats), _p(lens), _p(ws), coef_ptr, _p(dgamma), _p(dbeta), _p(dy),
+                                     B, Hh, Ww, Cc, _ACT[act], _stream()), "bn_act_bwd_lens")
+    return dy
 
 
 def gst_attn_fwd(q, k, v, heads):

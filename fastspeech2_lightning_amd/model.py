@@ -531,6 +531,25 @@ class FastSpeech2(_Base):
         self.plan_enabled = True     # False: every step of THIS model eager (FS2_PLAN=0: of every model)
         self.training = False
         self.env.training = False
+        self._style_lengths = False
+
+    # ---- length-aware style encoding in training and validation ---------------------------------------------------
+    @property
+    def style_lengths(self) -> bool:
+        """``True``: a training or validation step (``inference=False``) computes every utterance's style from its own
+        ``mel_lens[b]`` frames -- padded rows are zeroed in front of every convolution of the style encoder, its
+        BatchNorm statistics run over the valid positions only and the GRU stops after each utterance's own step count
+        (``StyleEncoder.fwd_train`` in train mode, the eval-mode ``StyleEncoder.fwd(mel, lens)`` in validation), so the
+        style does not depend on the batch's or the length bucket's padding.  ``False`` (the default): the reference's
+        definition, which reads the padding.  Inference paths are the same either way.  Needs the GST module."""
+        return self._style_lengths
+
+    @style_lengths.setter
+    def style_lengths(self, on):
+        if on and self.gst is None:
+            raise ValueError("style_lengths needs a model with the global style token module "
+                             "(model.use_global_style_token_module)")
+        self._style_lengths = bool(on)
 
     # ---- helpers ------------------------------------------------------------------------------------
     def data_parallel(self, sync, rank: int):
@@ -742,6 +761,14 @@ class FastSpeech2(_Base):
                     style, _ = self.gst.fwd(self._dev(ref_mel, torch.float32))
                 elif inference and not teacher_forcing:
                     style = self.gst.condition_on_gst_tokens(B)
+                elif self._style_lengths and not inference:
+                    # every utterance's style from its own mel_lens[b] frames (the lengths stay on the device: a replayed
+                    # plan reads those of the batch it is fed); the encoder works on a copy of the target mel
+                    with self._prec("gst"):
+                        if self.training:
+                            style, gst_ctx = self.gst.fwd_train(batch["mel"], batch["mel_lens"])
+                        else:
+                            style, _ = self.gst.fwd(H.axpby(batch["mel"], None, 1.0, 0.0), batch["mel_lens"])
                 else:
                     with self._prec("gst"):
                         style, gst_ctx = self.gst.fwd(batch["mel"])
@@ -998,7 +1025,8 @@ class FastSpeech2(_Base):
         weights = (t.pitch_loss_weight, t.energy_loss_weight, t.duration_loss_weight, t.mel_loss_weight,
                    t.postnet_loss_weight, t.attn_ctc_loss_weight, t.attn_bin_loss_weight)
         return (tuple(geo), self.precision, bool(self.env.side_enabled), tuple(PRED_LANES.values()), id(sync) if sync else 0, bin_w, weights,
-                getattr(self.postnet, "dropout_p", None), M.BF16_CHAIN, M.PRED_STORED, M.POSTNET_IM2COL, FP32_TRANSPOSED, HOLD_WGRADS, EARLY_FLUSH, PRED_GROUP, M.WGRAD_GROUP_ROWS, H.GEMM_GROUP, self.env.seed, H.plan_flags())
+                getattr(self.postnet, "dropout_p", None), M.BF16_CHAIN, M.PRED_STORED, M.POSTNET_IM2COL, FP32_TRANSPOSED, HOLD_WGRADS, EARLY_FLUSH, PRED_GROUP, M.WGRAD_GROUP_ROWS, H.GEMM_GROUP, self.env.seed, H.plan_flags(),
+                bool(self._style_lengths))
 
     def _frame_level_targets(self) -> dict:
         """Whether the batch's pitch / energy targets run along the mel axis (they do for a model that learns the

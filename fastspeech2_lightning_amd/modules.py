@@ -258,6 +258,12 @@ class BatchNorm:
         # num_batches_tracked is advanced once per training forward for all layers (ParamStore.bn_counters)
         return st
 
+    def stats_lens(self, raw, lens):
+        """Training statistics over the valid positions of ``raw`` [B, H, W, C] only (``hip.bn_stats_lens``)."""
+        S, p = self.S, self.prefix
+        return H.bn_stats_lens(raw, lens, S.p(p + "weight"), S.p(p + "bias"), S.b(p + "running_mean"),
+                               S.b(p + "running_var"))
+
     def grads(self):
         return self.S.g(self.prefix + "weight"), self.S.g(self.prefix + "bias")
 
@@ -883,8 +889,46 @@ class StyleEncoder:
         v = H.linear_fwd(tk, *self._lw("v"))
         p, ctx = H.gst_attn_fwd(q, k, v, self.HEADS)
         style = H.linear_fwd(ctx, *self._lw("out"))
-        return style, Ctx(conv=conv_saved, feat=feat, hs=hs, gates=gates, q=q, tk=tk, k=k, v=v, p=p, ctx=ctx,
-                          shape=(B, Hh, Ww, C))
+        return style, Ctx(conv=conv_saved, feat=feat, hs=hs, gates=gates, ref=ref, q=q, tk=tk, k=k, v=v, p=p, ctx=ctx,
+                          shape=(B, Hh, Ww, C), table=None)
+
+    def fwd_train(self, mel, lens):
+        """The length-aware TRAINING forward: every row's style is what its first ``lens[b]`` frames give, and ``bwd`` is
+        the exact gradient of that.  With ``hip.conv_s2_lens``'s row counts L_l: rows ``t >= L_l[b]`` of every
+        convolution's input are zeroed (``hip.zero_tail_rows``; the mel in a copy -- the caller's tensor is the loss's
+        target), BatchNorm takes its batch statistics over the positions ``t < L_{l+1}[b]`` only
+        (``hip.bn_stats_lens``: count ``W_{l+1} * sum_b L_{l+1}[b]``, running buffers with the unbiased variance of that
+        count), and the GRU is ONE ``hip.gru_fwd_states`` launch that stops every row after its own ``L_6`` steps and
+        keeps the states and gates.  ``lens`` [B] int32 stays in GPU memory: a launch plan recorded from this forward
+        reads the lengths of the batch it is fed."""
+        S, env, U = self.S, self.env, self.U
+        if not env.training:
+            raise ValueError("StyleEncoder.fwd_train needs a model in train mode (eval mode: fwd(mel, lens))")
+        B, T, F = mel.shape
+        n = len(self.convs)
+        table = H.conv_s2_lens(lens, n)
+        x = H.axpby(mel, None, 1.0, 0.0).view(B, T, F, 1)
+        conv_saved = []
+        for i, (w, bn, c) in enumerate(self.convs):
+            H.zero_tail_rows(x, table[i], B, x.shape[1])
+            raw = H.conv2d_s2_fwd(x, S.p(w))
+            rows = raw.numel() // c
+            stats = bn.stats_lens(raw, table[i + 1])
+            y = H.bn_act_fwd(raw.view(rows, c), stats, "relu").view(raw.shape)
+            conv_saved.append((x, raw, stats))
+            x = y
+        _, Hh, Ww, C = x.shape
+        feat = x.view(B * Hh, Ww * C)   # (rows beyond L_6 are finite and meet zero gradient rows only)
+        gi = H.linear_fwd(feat, S.p(self.wih), S.p(self.bih))            # rows (b, t)
+        ref, hs, gates = H.gru_fwd_states(gi.view(B, Hh, 3 * U), S.p(self.whh), S.p(self.bhh), table[n])
+        q = H.linear_fwd(ref, *self._lw("q"))
+        tk = H.act_apply(S.p(self.embs), "tanh")
+        k = H.linear_fwd(tk, *self._lw("k"))
+        v = H.linear_fwd(tk, *self._lw("v"))
+        p, ctx = H.gst_attn_fwd(q, k, v, self.HEADS)
+        style = H.linear_fwd(ctx, *self._lw("out"))
+        return style, Ctx(conv=conv_saved, feat=feat, hs=hs, gates=gates, ref=ref, q=q, tk=tk, k=k, v=v, p=p, ctx=ctx,
+                          shape=(B, Hh, Ww, C), table=table)
 
     def _fwd_lens(self, mel, lens):
         """The length-aware inference forward.  ``hip.conv_s2_lens`` gives every layer's row counts L_l; rows ``t >= L_l[b]``
@@ -946,8 +990,10 @@ class StyleEncoder:
         dtk = H.axpby(dtk, H.linear_bwd_data(dv, self._lw("v")[0]))
         H.axpby(H.dact_mul(dtk, S.p(self.embs), "tanh"), None, 1.0, 0.0, out=S.g(self.embs))
         gw, gb = g("q")
-        H.linear_bwd_weight(dq, c.hs[Hh], gw, bias_grad=gb)
+        H.linear_bwd_weight(dq, c.ref, gw, bias_grad=gb)
         dh = H.linear_bwd_data(dq, self._lw("q")[0])
+        if c.table is not None:
+            return self._bwd_lens(dh, c)
         # GRU backward through time
         dgi = torch.empty(B * Hh, 3 * U, device=dh.device, dtype=torch.float32)
         dgh_all = torch.empty(Hh, B, 3 * U, device=dh.device, dtype=torch.float32)
@@ -964,6 +1010,26 @@ class StyleEncoder:
             gg, gbb = bn.grads()
             draw = H.bn_act_bwd(d.reshape(rows, ch), raw.view(rows, ch), stats, gg, gbb, "relu", training=env.training)
             d = H.conv2d_s2_bwd(draw.view(raw.shape), x, S.p(w), S.g(w), need_dx=i > 0)
+
+    def _bwd_lens(self, dh, c):
+        """Below the style token layer, the backward of ``fwd_train``: the recurrence backwards in ONE launch
+        (``hip.gru_bwd_states``: gradient rows beyond a row's step count are exact zeros, so the weight gradients stay
+        GEMMs over all rows), then per layer ``hip.bn_act_bwd_lens``, whose sums run over the valid positions and which
+        writes zeros beyond them -- the gradient of a zeroed input row is zero."""
+        S, U = self.S, self.U
+        B, Hh, Ww, C = c.shape
+        n = len(self.convs)
+        dgi, dgh, _ = H.gru_bwd_states(dh, c.hs, c.gates, S.p(self.whh), c.table[n])
+        H.linear_bwd_weight(dgh.view(B * (Hh + 1), 3 * U), c.hs.view(B * (Hh + 1), U), S.g(self.whh), bias_grad=S.g(self.bhh))
+        dgi = dgi.view(B * Hh, 3 * U)
+        H.linear_bwd_weight(dgi, c.feat, S.g(self.wih), bias_grad=S.g(self.bih))
+        d = H.linear_bwd_data(dgi, S.p(self.wih)).view(B, Hh, Ww, C)
+        for i in range(n - 1, -1, -1):
+            w, bn, ch = self.convs[i]
+            x, raw, stats = c.conv[i]
+            gg, gbb = bn.grads()
+            draw = H.bn_act_bwd_lens(d.view(raw.shape), raw, stats, c.table[i + 1], gg, gbb, "relu")
+            d = H.conv2d_s2_bwd(draw, x, S.p(w), S.g(w), need_dx=i > 0)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -682,6 +682,43 @@ int fs2hip_gru_last_state(const float* gi, const float* w_hh, const float* b_hh,
                           int T, int U, void* stream);
 int fs2hip_conv_s2_lens(const int* lens, int* table, int B, int n, void* stream);
 
+/* Length-aware style encoding (training): every utterance's style from its own frames, with a backward pass.  All fp32,
+ * lengths read from device memory, no host synchronisation, no float atomics, deterministic.  FS2HIP_EINVAL, before any
+ * launch: a null pointer, a non-positive extent, U != 128, a misaligned tensor.
+ *   gru_fwd_states  gru_last_state kept for training: the same recurrence in the same arithmetic order (h_out is
+ *                   bit-equal), which also writes hs [B][T+1][U] (hs[b][0] = 0, hs[b][t+1] = the state after step t) and
+ *                   gates [B][T][4U] = (r, z, n, gh_n) per step.  Rows of gi at and beyond clamp(steps[b], 0, T) are never
+ *                   read; the rows of hs and gates beyond it are written as zeros.
+ *   gru_bwd_states  the whole backward through time in ONE launch, a workgroup per utterance: from dh_last [B][U] it
+ *                   writes dgi [B][T][3U] (gradient of gi), dgh [B][T+1][3U] (gradient of w_hh h_{t-1} + b_hh; row t
+ *                   pairs with hs[b][t], so dgh^T hs over all B * (T + 1) rows is the gradient of w_hh and dgh's column
+ *                   sums that of b_hh) and dh0 [B][U] (gradient of the initial state; dh_last where there is no step).
+ *                   Rows at and beyond an utterance's step count, row T of dgh included, are exact zeros.  The sums add
+ *                   in a fixed order and read that utterance alone: bit-equal whatever the batch.
+ * BatchNorm over the VALID positions of y [B][H][W][C] (channels last; C % 4 == 0, C <= 1024): utterance b keeps its first
+ * clamp(lens[b], 0, H) rows of H, and rows beyond them are never read (they may hold NaN).
+ *   bn_lens_parts   rows of the `partial` scratch [parts][2][C] both calls below take (0 for invalid extents)
+ *   bn_stats_lens   per-channel mean and biased variance over the N = W * sum_b L[b] valid positions (pivot-shifted
+ *                   stripes merged with Chan's formula in fp64, as colstats + bn_finalize), written as the stats [5][C]
+ *                   of bn_finalize (scale, shift, mean, invstd, eps) for bn_act_fwd; the running buffers (both or neither
+ *                   may be NULL) move with `momentum` and the unbiased variance N / (N - 1).  N = 0: mean 0, variance 0,
+ *                   running buffers untouched.
+ *   bn_act_bwd_lens backward of act(y * scale + shift) with those statistics: dgamma, dbeta, and dy [B][H][W][C] whose
+ *                   sums and 1 / N run over the valid positions; rows of dy beyond the lengths are written as zeros, rows
+ *                   of dout and y beyond them are never read.  coef: [2][C] scratch.  Up to 16 valid rows in all are
+ *                   taken in fp64 (as bn_act_bwd's few-row form). */
+int fs2hip_gru_fwd_states(const float* gi, const float* w_hh, const float* b_hh, const int* steps, float* hs, float* gates,
+                          float* h_out, int B, int T, int U, void* stream);
+int fs2hip_gru_bwd_states(const float* dh_last, const float* hs, const float* gates, const float* w_hh, const int* steps,
+                          float* dgi, float* dgh, float* dh0, int B, int T, int U, void* stream);
+int fs2hip_bn_lens_parts(int B, int H, int W);
+int fs2hip_bn_stats_lens(const float* y, const int* lens, float* partial, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, float momentum, float eps, float* stats, int B, int H,
+                         int W, int C, void* stream);
+int fs2hip_bn_act_bwd_lens(const float* dout, const float* y, const float* stats, const int* lens, float* partial,
+                           float* coef, float* dgamma, float* dbeta, float* dy, int B, int H, int W, int C, int act,
+                           void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
