@@ -69,10 +69,10 @@ __global__ __launch_bounds__(256) void bucket_embed_add_kernel(const float* __re
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= M) return;
   const float v = val[row] * control;
-  int lo = 0, hi = NB;  // lower_bound: number of edges strictly below v
+  int lo = 0, hi = NB;  // lower_bound: number of edges strictly below v; a NaN v takes bucket NB, as torch.bucketize
   while (lo < hi) {
     int mid = (lo + hi) >> 1;
-    if (bins[mid] < v) lo = mid + 1; else hi = mid;
+    if (!(bins[mid] >= v)) lo = mid + 1; else hi = mid;
   }
   if (lane == 0 && idx_out) idx_out[row] = lo;
   const float4* e = reinterpret_cast<const float4*>(W + (long long)lo * D);
@@ -108,10 +108,10 @@ __global__ __launch_bounds__(256) void bucket_embed_add_ctl_kernel(const float* 
     c = ctl[grp];
   }
   const float v = val[row] * c;
-  int lo = 0, hi = NB;  // lower_bound: number of edges strictly below v
+  int lo = 0, hi = NB;  // lower_bound: number of edges strictly below v; a NaN v takes bucket NB, as torch.bucketize
   while (lo < hi) {
     int mid = (lo + hi) >> 1;
-    if (bins[mid] < v) lo = mid + 1; else hi = mid;
+    if (!(bins[mid] >= v)) lo = mid + 1; else hi = mid;
   }
   if (lane == 0) {
     if (idx_out) idx_out[row] = lo;

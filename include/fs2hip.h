@@ -366,7 +366,8 @@ int fs2hip_embedding_fwd(const int* idx, const float* W, float* out, int M, int 
 /* embedding backward = fs2hip_onehot + fs2hip_gemm (dW = onehot^T @ dy; split-K weight-gradient mode):
  * out[m][v] = (idx[m] == v && v != padding_idx), row length Vp (multiple of 4, >= vocabulary) */
 int fs2hip_onehot(const int* idx, float* out, int M, int Vp, int padding_idx, void* stream);
-/* out = x + W[lower_bound(bins, val*control)]; idx_out (int32, bit-exact vs torch.bucketize) optional */
+/* out = x + W[lower_bound(bins, val*control)]; idx_out (int32, bit-exact vs torch.bucketize) optional.  A NaN value takes
+ * bucket NB, as in torch.bucketize (W has NB + 1 rows). */
 int fs2hip_bucket_embed_add(const float* val, float control, const float* bins, int NB, const float* W,
                             const float* x, float* out, int* idx_out, int M, int D, void* stream);
 /* The same with the control in device memory (a tensor in InferenceControl): row r uses ctl[r / ctl_div] -- ctl_div = 1:
