@@ -177,7 +177,13 @@ def build_parser() -> argparse.ArgumentParser:
     sy.add_argument("--return-scores", action="store_true",
                     help="with -T: also write OUTPUT_DIR/scores-<step>.psv, every utterance's own losses (as if it were scored alone: "
                          "implies --exact-lengths) and coverage scores, worst first (the reference's return_scores, batched)")
-    sy.add_argument("--scores-only", action="store_true", help="with --return-scores: write the score file and no spectrograms")
+    sy.add_argument("--compare-to", type=Path, default=None, metavar="DIR",
+                    help="with -f: also write OUTPUT_DIR/dtw-<step>.psv, every row's dynamic-time-warping distance between its "
+                         "FREE synthesis and its recorded mel DIR/spec/<basename>--... (the preprocessed folder -T would read), "
+                         "mean frame distance along the warping path, worst first (fs2hip_frame_dist + fs2hip_dtw; implies "
+                         "--exact-lengths).  Not with -T: teacher forcing fixes the lengths, --return-scores is its measure")
+    sy.add_argument("--scores-only", action="store_true",
+                    help="with --return-scores or --compare-to: write the score file and no spectrograms")
     sy.add_argument("--write-alignments", action="store_true",
                     help="also write OUTPUT_DIR/synthesized_alignment/*--alignment.pt: every text's tokens, per-token durations in "
                          "frames, and the pitch and energy predictions (a dict of tensors; fs2hip_pack_rows packs them into the "
@@ -815,9 +821,15 @@ def synthesize_command(args) -> int:
     if args.return_scores and args.teacher_forcing_directory is None:
         raise SystemExit("--return-scores needs --teacher-forcing-directory (-T): a loss is taken against the recorded mel and "
                          "durations, which free synthesis does not have")
-    if args.scores_only and not args.return_scores:
-        raise SystemExit("--scores-only goes with --return-scores")
-    from .data import (AlignmentWriter, PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores,
+    if args.compare_to is not None and args.teacher_forcing_directory is not None:
+        raise SystemExit("--compare-to scores free synthesis, whose length differs from the recording's; with "
+                         "--teacher-forcing-directory (-T) the lengths are the recording's and --return-scores gives the losses")
+    if args.compare_to is not None and args.texts:
+        raise SystemExit("--compare-to needs --filelist (-f): the recorded mel of a row is found by its basename, and a --text "
+                         "(-t) has none")
+    if args.scores_only and not (args.return_scores or args.compare_to is not None):
+        raise SystemExit("--scores-only goes with --return-scores or --compare-to")
+    from .data import (AlignmentWriter, DtwWriter, PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores,
                        synthesis_batches, synthesis_entries)
     print(f"Loading checkpoint from {args.model_path}", file=sys.stderr)
     if args.dry_run:
@@ -836,14 +848,15 @@ def synthesize_command(args) -> int:
     style, style_sources = style_references(entries, args.style_reference, args.filelist, config.preprocessing.audio.n_mels)
     dataset = SynthesisDataset(entries, config, model.lang2id, model.speaker2id,
                                teacher_forcing_dir=args.teacher_forcing_directory, style_reference=style,
-                               attn_prior=attn_prior_mode(args, config)["attn_prior"])
+                               attn_prior=attn_prior_mode(args, config)["attn_prior"], compare_dir=args.compare_to)
     sort = not args.no_sort
     scores = ScoreWriter(args.output_dir, global_step) if args.return_scores else None
+    compare = DtwWriter(args.output_dir, global_step) if args.compare_to is not None else None
     if args.dry_run:
         plan = {
             "checkpoint": str(args.model_path), "global_step": global_step, "output_dir": str(args.output_dir),
             "utterances": len(dataset), "batch_size": args.batch_size, "sort": sort,
-            "exact_lengths": bool(args.exact_lengths or args.return_scores),
+            "exact_lengths": bool(args.exact_lengths or args.return_scores or compare is not None),
             "return_scores": bool(args.return_scores), **attn_prior_mode(args, config),
             "token_counts": dataset.token_counts, "dropped_symbols": dataset.dropped,
             "batches": synthesis_batches(dataset.token_counts, args.batch_size, sort),
@@ -857,6 +870,9 @@ def synthesize_command(args) -> int:
             plan["scores_file"] = str(scores.path)
             for e, cov in zip(plan["entries"], coverage_scores(dataset.tokens)):
                 e.update(cov)
+        if compare is not None:
+            plan["compare_to"] = str(args.compare_to)
+            plan["dtw_file"] = str(compare.path)
         if args.write_alignments:
             plan["alignment_files"] = alignment_file_names(dataset, args.output_dir, global_step)
             if dataset.teacher_forcing and config.model.learn_alignment:
@@ -876,13 +892,15 @@ def synthesize_command(args) -> int:
     control = InferenceControl(pitch=args.pitch_control, energy=args.energy_control, duration=args.duration_control)
     t0 = time.perf_counter()
     res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort, exact_lengths=args.exact_lengths,
-                     scores=scores, alignments=alignments)
+                     scores=scores, alignments=alignments, compare=compare)
     torch.cuda.synchronize()
     report = {"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
               "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),
               "output_dir": str(writer.dir if writer is not None else args.output_dir)}
     if scores is not None:
         report["scores_file"] = str(scores.close())
+    if compare is not None:
+        report["dtw_file"] = str(compare.close())
     if alignments is not None:
         report["alignment_files"] = len(res["alignment_files"])
     print(json.dumps(report), flush=True)

@@ -16,17 +16,6 @@ namespace {
 
 constexpr float NEG_INF = -INFINITY;
 
-// lane i <- lane i-1 (lane 0 gets `fill`) / lane i <- lane i+1 (lane 63 gets `fill`): one DPP move instead of a
-// ds_bpermute round trip through the LDS crossbar -- these sit on the serial critical path of the recursions below
-__device__ __forceinline__ float wave_shr1(float x, float fill) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, x),
-                                                               0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float wave_shl1(float x, float fill) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, x),
-                                                               0x130, 0xf, 0xf, false));
-}
-
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void attn_dist_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                          float* __restrict__ logits, int B, int T1, int T2, int C) {
@@ -271,8 +260,8 @@ __global__ __launch_bounds__(64) void mas_wave_kernel(const float* __restrict__ 
       const int i = i0 + r;
       if (i >= T1) break;  // uniform
       const float a63 = __shfl(pa, 63, 64);                 // column 64's left neighbour is column 63
-      const float la = wave_shr1(pa, NEG_INF);              // column 0 has no left neighbour
-      const float lb = wave_shr1(pb, a63);
+      const float la = fs2_wave_shr1(pa, NEG_INF);          // column 0 has no left neighbour
+      const float lb = fs2_wave_shr1(pb, a63);
       const bool left_a = acta && ja > 0 && la >= pa;  // fs2/attn/alignment.py:68 (ties move left)
       const bool left_b = actb && lb >= pb;
       const float xa = va[r] + fmaxf(la, pa), xb = vb[r] + fmaxf(lb, pb);

@@ -131,6 +131,21 @@ __device__ __forceinline__ float fs2_wave_max(float v) {
   return v;
 }
 
+// ---- one-lane wavefront shifts ------------------------------------------------------------
+// lane i <- lane i-1 (lane 0 gets `fill`) / lane i <- lane i+1 (lane 63 gets `fill`): one DPP move instead of a
+// ds_bpermute round trip through the LDS crossbar -- these sit on the serial critical path of the recursions that walk
+// a dynamic programme with one wavefront (aligner.hip's alignment search, dtw.hip)
+__device__ __forceinline__ int fs2_wave_shr1(int x, int fill) {
+  return __builtin_amdgcn_update_dpp(fill, x, 0x138, 0xf, 0xf, false);
+}
+__device__ __forceinline__ float fs2_wave_shr1(float x, float fill) {
+  return __builtin_bit_cast(float, fs2_wave_shr1(__builtin_bit_cast(int, x), __builtin_bit_cast(int, fill)));
+}
+__device__ __forceinline__ float fs2_wave_shl1(float x, float fill) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, fill), __builtin_bit_cast(int, x),
+                                                               0x130, 0xf, 0xf, false));
+}
+
 // ---- shared host-side launchers (reduce.hip) ----------------------------------------------------
 // out0[c] = sum over rows of src[r*stride + c] for c < n0, out1[c - n0] for n0 <= c < n
 int fs2_reduce_rows(const float* src, int rows, int n, long long stride, float* out0, int n0, float* out1,

@@ -689,6 +689,59 @@ class ScoreWriter:
         return self.path
 
 
+class DtwWriter:
+    """``<output_dir>/dtw-<global_step>.psv``: how far free synthesis is from the recording, one '|'-separated row per
+    dataset entry, worst first.  ``total`` and ``steps`` are what ``FastSpeech2.mel_dtw`` gives for the entry (the
+    accumulated frame distance along the cheapest warping path and the cells on it), ``mel_dtw = total / steps`` the
+    mean distance per aligned frame pair, ``frames`` / ``ref_frames`` the synthesized and recorded lengths and
+    ``frame_ratio`` their quotient.  ``mel_dtw`` and ``frame_ratio`` are empty fields when ``steps`` or ``ref_frames`` is 0.
+    Rows are sorted by ``-mel_dtw``, rows without one last, ties in input order.  ``add`` collects a record in any order
+    (``position``: the entry's place in the input); ``close`` sorts, writes and returns the path."""
+
+    FIELDS = ("basename", "speaker", "language", "mel_dtw", "total", "steps", "frames", "ref_frames", "frame_ratio", "raw_text")
+
+    def __init__(self, output_dir, global_step: int = 0):
+        self.dir, self.global_step = Path(output_dir), int(global_step)
+        self.records = {}
+
+    @property
+    def path(self) -> Path:
+        return self.dir / f"dtw-{self.global_step}.psv"
+
+    def add(self, position: int, record: dict):
+        """``record``: basename, speaker, language, raw_text, ``total`` (float), ``steps``, ``frames``, ``ref_frames``
+        (ints); ``mel_dtw`` and ``frame_ratio`` are derived here."""
+        position = int(position)
+        if position in self.records:
+            raise ValueError(f"DtwWriter: position {position} delivered twice")
+        missing = [k for k in ("basename", "total", "steps", "frames", "ref_frames") if k not in record]
+        if missing:
+            raise ValueError(f"DtwWriter: the record of position {position} lacks {missing}")
+        rec = dict(record)
+        for k in ("steps", "frames", "ref_frames"):
+            rec[k] = int(rec[k])
+        rec["total"] = float(rec["total"])
+        rec["mel_dtw"] = rec["total"] / rec["steps"] if rec["steps"] > 0 else None
+        rec["frame_ratio"] = rec["frames"] / rec["ref_frames"] if rec["ref_frames"] > 0 else None
+        self.records[position] = rec
+
+    def sorted_records(self) -> list[dict]:
+        rows = [self.records[p] for p in sorted(self.records)]
+        rows.sort(key=lambda r: (r["mel_dtw"] is None, -r["mel_dtw"] if r["mel_dtw"] is not None else 0.0))
+        return rows
+
+    def close(self) -> Path:
+        import csv
+        self.dir.mkdir(parents=True, exist_ok=True)
+        with open(self.path, "w", encoding="utf8", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=list(self.FIELDS), delimiter="|", restval="", extrasaction="ignore",
+                               lineterminator="\n")
+            w.writeheader()
+            for r in self.sorted_records():
+                w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in r.items() if v is not None})
+        return self.path
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # synthesis: text -> inference items -> batches (reference fs2/cli/synthesize.py:136-319, fs2/dataset.py:88-224)
 # ----------------------------------------------------------------------------------------------------------------------
@@ -825,10 +878,15 @@ class SynthesisDataset(torch.utils.data.Dataset):
     per entry -- a sequence in entry order, or a mapping by basename: every item then carries its own reference, and a
     batch of them carries their frame counts (``style_reference_lens``).  Entries given the same object share
     it; when all do, this is the single shared reference again.  Every text is encoded in the constructor:
-    ``token_counts`` is what ``synthesis_batches`` takes."""
+    ``token_counts`` is what ``synthesis_batches`` takes.
+
+    ``compare_dir`` (free synthesis only): every item also carries ``compare_mel`` ``[frames, n_mels]``, the entry's
+    recorded mel from ``<compare_dir>/spec`` -- the file ``teacher_forcing_dir`` would load, found by the same
+    ``feature_path`` rule -- for ``synthesize(..., compare=DtwWriter)``.  A missing file is an error that names the
+    utterance.  The unit is the filelist row: its basename names the recording."""
 
     def __init__(self, entries: list[dict], config, lang2id: dict, speaker2id: dict, teacher_forcing_dir=None,
-                 style_reference=None, text_processor=None, attn_prior: str = "files"):
+                 style_reference=None, text_processor=None, attn_prior: str = "files", compare_dir=None):
         import sys
 
         from .config import TargetTrainingTextRepresentationLevel as L
@@ -841,6 +899,10 @@ class SynthesisDataset(torch.utils.data.Dataset):
         m, audio = config.model, config.preprocessing.audio
         self.teacher_forcing = teacher_forcing_dir is not None
         self.save_dir = Path(teacher_forcing_dir) if self.teacher_forcing else None
+        if compare_dir is not None and self.teacher_forcing:
+            raise ValueError("compare_dir cannot be combined with teacher_forcing_dir: a teacher-forced spectrogram has the "
+                             "recording's own length, and the losses against it already exist (ScoreWriter)")
+        self.compare_dir = Path(compare_dir) if compare_dir is not None else None
         self.sampling_rate = audio.input_sampling_rate
         self.spec_type = getattr(audio, "spec_type", "mel-librosa")
         self.chars = m.target_text_representation_level == L.characters
@@ -935,7 +997,7 @@ class SynthesisDataset(torch.utils.data.Dataset):
             if self.use_pfs:
                 pfs = self._load(bn, speaker, language, "pfs", "pfs.pt")
         last = item.get("is_last_input_chunk")
-        return {
+        out = {
             "mel": mel, "mel_style_reference": self.style if self.styles is None else self.styles[index],
             "duration": duration,
             "duration_control": item.get("duration_control", 1.0), "pfs": pfs, "text": self.tokens[index],
@@ -945,6 +1007,14 @@ class SynthesisDataset(torch.utils.data.Dataset):
             "energy": None, "pitch": None,
             "is_last_input_chunk": True if last is None else bool(last),
         }
+        if self.compare_dir is not None:
+            path = feature_path(self.compare_dir, "spec", bn, speaker, language, f"spec-{self.sampling_rate}-{self.spec_type}.pt")
+            try:
+                ref = torch.load(path, weights_only=True)
+            except FileNotFoundError:
+                raise FileNotFoundError(f"utterance {bn!r} has no recorded mel to compare to: {path} does not exist") from None
+            out["compare_mel"] = _style_mel(ref, self.config.preprocessing.audio.n_mels, f"recorded mel of utterance {bn!r}")
+        return out
 
 
 def slugify(text: str) -> str:

@@ -161,6 +161,8 @@ SIGNATURES = {
     "fs2hip_bn_lens_parts": "iii",
     "fs2hip_bn_stats_lens": "pppppppffpiiiip",
     "fs2hip_bn_act_bwd_lens": "pppppppppiiiiip",
+    "fs2hip_frame_dist": "pppppiiiip",
+    "fs2hip_dtw": "pppppiiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -2254,6 +2256,62 @@ def mas(x, in_lens, out_lens, is_log=False):
     _ok(lib().fs2hip_mas(_p(x), int(is_log), _p(in_lens), _p(out_lens), _p(hard), _p(hard_idx), _p(dur), _p(dirs), B, Tm,
                          Ts, _stream()), "mas")
     return hard, hard_idx, dur
+
+
+# ------------------------------------------------------------------------------------------
+# dynamic time warping between frame sequences of different lengths (dtw.hip)
+# ------------------------------------------------------------------------------------------
+FRAME_DIST_MAX_C = 204  # FS2_FRAME_DIST_MAX_C
+DTW_MAX_T1 = 6144       # FS2_DTW_MAX_T1
+
+
+def _dtw_lens(what, lens1, lens2, B):
+    _chk(lens1, torch.int32, f"{what}: the first lengths"); _chk(lens2, torch.int32, f"{what}: the second lengths")
+    _req(lens1.numel() == B and lens2.numel() == B,
+         f"{what}: {lens1.numel()} and {lens2.numel()} lengths for {B} utterances")
+
+
+def frame_dist(a, a_lens, b, b_lens, out=None):
+    """cost [B, T1, T2] fp32: ``cost[u, i, j] = sqrt(sum_c (a[u, i, c] - b[u, j, c])^2)`` for ``i < a_lens[u]``, ``j <
+    b_lens[u]`` (lengths int32 in GPU memory, clamped to the geometry on the device); the rest of ``out`` is left as it
+    is, and rows of ``a`` / ``b`` beyond the lengths are never read (``fs2hip_frame_dist``)."""
+    _chk(a, name="frame_dist: a"); _chk(b, name="frame_dist: b")
+    _req(a.dim() == 3 and b.dim() == 3 and a.shape[0] == b.shape[0] and a.shape[2] == b.shape[2],
+         f"frame_dist: a {tuple(a.shape)} and b {tuple(b.shape)} are not [B, T1, C] and [B, T2, C]")
+    B, T1, Cc = a.shape
+    T2 = b.shape[1]
+    _req(B > 0 and T1 > 0 and T2 > 0 and Cc > 0, f"frame_dist: empty geometry (B {B}, T1 {T1}, T2 {T2}, C {Cc})")
+    _req(B <= 65535, f"frame_dist: B = {B}: at most 65535 utterances per call")
+    _req(Cc <= FRAME_DIST_MAX_C, f"frame_dist: C = {Cc}: at most {FRAME_DIST_MAX_C} channels (the tiles' LDS)")
+    _dtw_lens("frame_dist", a_lens, b_lens, B)
+    if out is None:
+        out = torch.empty(B, T1, T2, device=a.device, dtype=torch.float32)
+    else:
+        _chk(out, name="frame_dist: out")
+        _req(tuple(out.shape) == (B, T1, T2), f"frame_dist: out is {tuple(out.shape)}, expected {(B, T1, T2)}")
+    _ok(lib().fs2hip_frame_dist(_p(a), _p(a_lens), _p(b), _p(b_lens), _p(out), B, T1, T2, Cc, _stream()), "frame_dist")
+    return out
+
+
+def dtw(cost, lens1, lens2, total=None, steps=None):
+    """(total [B] fp32, steps [B] int32): the accumulated cost of the cheapest monotone path through every utterance's
+    ``lens1[u] x lens2[u]`` box of ``cost`` [B, T1, T2] and the number of cells on it -- diagonal, then up, then left,
+    each taken only when strictly cheaper (``fs2hip_dtw``; include/fs2hip.h has the recursion).  An empty box gives (0,
+    0).  Bit-exact from ``cost``; one wavefront per utterance."""
+    _chk(cost, name="dtw: cost")
+    _req(cost.dim() == 3 and cost.numel() > 0, f"dtw: cost {tuple(cost.shape)} is not a non-empty [B, T1, T2]")
+    B, T1, T2 = cost.shape
+    _req(T1 <= DTW_MAX_T1, f"dtw: T1 = {T1}: at most {DTW_MAX_T1} rows (8 bytes of LDS per row beside the cost ring)")
+    _dtw_lens("dtw", lens1, lens2, B)
+    if total is None:
+        total = torch.empty(B, device=cost.device, dtype=torch.float32)
+    if steps is None:
+        steps = torch.empty(B, device=cost.device, dtype=torch.int32)
+    _chk(total, name="dtw: total"); _chk(steps, torch.int32, "dtw: steps")
+    _req(total.numel() == B and steps.numel() == B,
+         f"dtw: total has {total.numel()} and steps {steps.numel()} entries for {B} utterances")
+    _ok(lib().fs2hip_dtw(_p(cost), _p(lens1), _p(lens2), _p(total), _p(steps), B, T1, T2, _stream()), "dtw")
+    return total, steps
 
 
 def duration_cumsum(dur, Tm, expect=None, bad_count=None):

@@ -1397,6 +1397,47 @@ class FastSpeech2(_Base):
             table = H.utterance_losses(terms, B, bin_term=bin_term, ctc_term=ctc_term, out=out)
         return table, tuple(keys)
 
+    def mel_dtw(self, output, ref, ref_lens, out=None):
+        """Dynamic-time-warping distance between an inference forward's spectrograms and recorded ones of other lengths:
+        ``(total, steps)``, ``[B]`` fp32 and ``[B]`` int32 in GPU memory.  For utterance b the frames are the first
+        ``output["tgt_lens"][b]`` rows of ``output[self.output_key]`` and the first ``ref_lens[b]`` rows of ``ref`` ``[B, Tr,
+        n_mels]`` (the recorded mel in the model's feature space, time first); the cost of a frame pair is their Euclidean
+        distance, ``total`` the accumulated cost of the cheapest monotone path and ``steps`` the number of cells on it
+        (``hip.frame_dist`` + ``hip.dtw``: diagonal, then one more synthesized frame, then one more recorded frame, each
+        taken only when strictly cheaper), so ``total / steps`` is the mean distance per aligned pair.  An utterance
+        without frames on either side gives (0, 0).  fp32 arithmetic on whatever the forward produced; two launches,
+        nothing is read back.  ``out``: a ``2 * B`` fp32 device vector to fill instead of fresh tensors -- the totals, then
+        the step counts as int32 bit patterns (``synthesize`` hands in a piece of the buffer that leaves the GPU with the
+        spectrograms).  The cost matrices live in a persistent buffer that only grows."""
+        if self.training:
+            raise ValueError("mel_dtw needs a model in eval mode (model.eval()): the distance is an inference result")
+        y, lens = output.get(self.output_key), output.get("tgt_lens")
+        if y is None or lens is None or y.dim() != 3:
+            raise ValueError(f"mel_dtw: the output has no [B, Tm, n_mels] {self.output_key!r} with tgt_lens -- run "
+                             "forward(batch, inference=True) first")
+        with torch.cuda.device(self.device_):
+            self.env.join()
+            y = y if y.dtype == torch.float32 else y.float()
+            ref, ref_lens = self._dev(ref, torch.float32), self._dev(ref_lens, torch.int32)
+            B, Tm, _ = y.shape
+            if not torch.is_tensor(ref) or ref.dim() != 3 or ref.shape[0] != B or ref.shape[2] != y.shape[2]:
+                raise ValueError(f"mel_dtw: ref must be [B = {B}, Tr, n_mels = {y.shape[2]}], got "
+                                 f"{list(ref.shape) if torch.is_tensor(ref) else type(ref).__name__}")
+            Tr = ref.shape[1]
+            total = steps = None
+            if out is not None:
+                if out.dtype != torch.float32 or out.numel() != 2 * B:
+                    raise ValueError(f"mel_dtw: out must be {2 * B} fp32 values (B totals, B step counts)")
+                out = out.view(-1)
+                total, steps = out[:B], out[B:].view(torch.int32)
+            if Tr == 0 or Tm == 0:   # nothing recorded (or synthesized) in the whole batch
+                total = H.zeros(B, device=y.device) if total is None else total.zero_()
+                steps = H.zeros(B, device=y.device, dtype=torch.int32) if steps is None else steps.zero_()
+                return total, steps
+            cost = H.persistent_buffer("mel_dtw_cost", torch.float32, B * Tm * Tr)[:B * Tm * Tr].view(B, Tm, Tr)
+            H.frame_dist(y.contiguous(), lens, ref, ref_lens, out=cost)
+            return H.dtw(cost, lens, ref_lens, total=total, steps=steps)
+
     def configure_optimizers(self):
         """fs2/model.py:530-549: ``([AdamW], [{"scheduler": NoamLR, "interval": "step"}])`` -- here a
         ``torch.optim.Optimizer`` whose ``step()`` is the fused clip + AdamW + schedule launch over the flat buffers and

@@ -39,6 +39,14 @@ token-level members by ``src_lens``, frame-level ones by ``tgt_lens``, their off
 comes from lengths the host already has (the collated ``src_lens``, the frame totals above), so the batch still leaves in
 the one copy and is waited for once; the device's offsets are checked against the host's, as the spectrograms' are.
 Without ``alignments`` not one launch, allocation or header byte changes.
+
+``compare`` (a ``data.DtwWriter``; ``fs2l synthesize --compare-to DIR``) scores FREE synthesis against the recordings: the
+dataset (``SynthesisDataset(..., compare_dir=DIR)``) attaches every entry's recorded mel, the batch's references go up
+with one non-blocking copy, and ``FastSpeech2.mel_dtw`` writes every utterance's dynamic-time-warping distance to its
+recording -- ``B`` totals and ``B`` step counts -- where the score table would be, at the end of the slot header (the two
+never occur together: scores need teacher forcing, which fixes the lengths and makes warping pointless).  So the batch
+still leaves in the one copy and is waited for once.  ``exact_lengths`` is forced on, as for scores.  The unit is the
+dataset entry, i.e. the filelist row.  Without ``compare`` not one launch, allocation or header byte changes.
 """
 from __future__ import annotations
 
@@ -55,7 +63,8 @@ class _Slot:
     """One device buffer + its pinned host twin, both float32: [header | alignment block | payload].  The header holds the
     batch's B + 1 int64 offsets (2 floats each, rounded up to 4 floats so that what follows starts 16-byte aligned), then
     -- when alignments are written -- one such table per member of the alignment block, and, when the batch is scored,
-    its [B, 8] table of per-utterance losses last.  The alignment block (only with alignments) holds the members' packed
+    its [B, 8] table of per-utterance losses last -- or, when the batch is compared to recordings, its B DTW totals and B
+    step counts there instead.  The alignment block (only with alignments) holds the members' packed
     rows back to back and is rounded up to 4 floats, so the payload starts 16-byte aligned with or without it."""
 
     def __init__(self, device):
@@ -66,8 +75,13 @@ class _Slot:
         return -(-2 * (B + 1) // 4) * 4
 
     @staticmethod
-    def header(B: int, scored: bool = False, members: int = 0) -> int:
-        return (1 + members) * _Slot.table(B) + (_COLS * B if scored else 0)
+    def header(B: int, scored: bool = False, members: int = 0, compared: bool = False) -> int:
+        return (1 + members) * _Slot.table(B) + (_COLS * B if scored else 0) + (_Slot.dtw_table(B) if compared else 0)
+
+    @staticmethod
+    def dtw_table(B: int) -> int:
+        """B totals then B step counts (int32 bit patterns), rounded up to 4 floats like every part of the header."""
+        return -(-2 * B // 4) * 4
 
     def reserve(self, floats: int):
         if self.dev is None or self.dev.numel() < floats:
@@ -80,7 +94,7 @@ _COLS = len(LOSS_KEYS) + 1   # columns of the score table: the loss terms and th
 
 
 def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2,
-               exact_lengths: bool = False, scores=None, alignments=None) -> dict:
+               exact_lengths: bool = False, scores=None, alignments=None, compare=None) -> dict:
     """Synthesizes every item of ``dataset`` (``data.SynthesisDataset``) and writes the spectrograms through ``writer``
     (``data.PackedSpecWriter``), in input order.  Returns ``{"files": [paths], "utterances": n, "frames": n, "batches": n}``.
     Per batch the host reads the GPU once inside the forward pass (the frame totals; nothing for a teacher-forced batch)
@@ -89,13 +103,25 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
     teacher-forced, ``exact_lengths`` is forced on, and ``writer`` may be None (scores only).  ``alignments``
     (``data.AlignmentWriter``): every text's durations, pitch and energy are written through it (the result gains
     ``"alignment_files"``, and ``"duration_files"`` for a teacher-forced dataset of a model that learns its alignment);
-    ``writer`` may be None here too.  At least one of the three is required."""
+    ``writer`` may be None here too.  ``compare`` (``data.DtwWriter``): every entry's DTW distance between its free
+    synthesis and its recorded mel is added to it (the caller closes it); the dataset must carry the recordings
+    (``SynthesisDataset(..., compare_dir=...)``, so it is not teacher-forced), ``exact_lengths`` is forced on, and
+    ``writer`` may be None (comparison only).  At least one of the four is required."""
     if depth < 1:
         raise ValueError("synthesize: depth >= 1")
-    if writer is None and scores is None and alignments is None:
+    if writer is None and scores is None and alignments is None and compare is None:
         raise ValueError("synthesize: a PackedSpecWriter is required (or a ScoreWriter as scores=, or an AlignmentWriter as "
                          "alignments=): there is nothing to write")
     scored = scores is not None
+    compared = compare is not None
+    if compared:
+        if getattr(dataset, "teacher_forcing", False):
+            raise ValueError("synthesize: compare= scores free synthesis; a teacher-forced dataset already has the "
+                             "recording's lengths, and its losses are what scores= writes")
+        if getattr(dataset, "compare_dir", None) is None:
+            raise ValueError("synthesize: compare= needs a dataset that carries the recorded mels "
+                             "(SynthesisDataset(..., compare_dir=...))")
+        exact_lengths = True
     if scored:
         if not getattr(dataset, "teacher_forcing", False):
             raise ValueError("synthesize: scores need a teacher-forced dataset (SynthesisDataset(..., teacher_forcing_dir=...)): "
@@ -120,12 +146,12 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
         levels = {"duration": "phone", "pitch": vp.pitch.level.value, "energy": vp.energy.level.value}
         teacher_forced = bool(getattr(dataset, "teacher_forcing", False))
         duration_source = ("aligner" if learn_alignment else "given") if teacher_forced else "predicted"
-    # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys, alignment block)], oldest first
+    # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys, alignment block, recorded frame counts)], oldest first
     pending = []
 
     def finish(job):
         nonlocal frames
-        slot, event, hdr, total, expect, cpu_batch, positions, keys, block = job
+        slot, event, hdr, total, expect, cpu_batch, positions, keys, block, ref_frames = job
         event.synchronize()   # the one wait of this batch
         base = hdr
         if writer is not None:
@@ -154,6 +180,15 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 rec = dict(basename=name, speaker=speaker, language=language, raw_text=text, total=row[-1], **coverage[pos])
                 rec.update((k, row[LOSS_KEYS.index(k)]) for k in keys)
                 scores.add(pos, rec)
+        if compared:
+            B = len(positions)
+            at = hdr - _Slot.dtw_table(B)
+            totals = slot.host[at:at + B].tolist()
+            cells = slot.host[at + B:at + 2 * B].view(torch.int32).tolist()
+            for k, pos in enumerate(positions):
+                compare.add(pos, dict(basename=cpu_batch["basename"][k], speaker=cpu_batch["speaker"][k],
+                                      language=cpu_batch["language"][k], raw_text=cpu_batch["raw_text"][k], total=totals[k],
+                                      steps=cells[k], frames=(expect[k + 1] - expect[k]) // n_mels, ref_frames=ref_frames[k]))
         frames += expect[-1] // n_mels
         if writer is not None:
             files.extend(writer.write_packed(slot.host[base:base + total], offsets, cpu_batch, positions))
@@ -168,7 +203,14 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 if own_target_style:
                     cpu_batch["mel_style_reference"] = cpu_batch["mel"]
                     cpu_batch["style_reference_lens"] = cpu_batch["mel_lens"]
-                out = model(cpu_batch, _copy_control(control), inference=True, exact_lengths=exact_lengths)
+                fwd_batch, ref_frames = cpu_batch, None
+                if compared:
+                    # the recordings are not the forward's business: they go up on their own, in one copy
+                    fwd_batch = {k: v for k, v in cpu_batch.items() if k not in ("compare_mel", "compare_lens")}
+                    ref = cpu_batch["compare_mel"].to(device, non_blocking=True)
+                    ref_lens = cpu_batch["compare_lens"].to(device, non_blocking=True)
+                    ref_frames = cpu_batch["compare_lens"].tolist()
+                out = model(fwd_batch, _copy_control(control), inference=True, exact_lengths=exact_lengths)
                 y = out[model.output_key]
                 B, Tm, C = y.shape
                 if cpu_batch["mel_lens"] is not None:
@@ -178,8 +220,8 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 expect = [0]
                 for n in lens_host.tolist():
                     expect.append(expect[-1] + int(n) * C)
-                hdr = _Slot.header(B, scored, len(levels) if aligned else 0)
-                total = expect[-1] if writer is not None else 0   # (scores only: the header is all that travels)
+                hdr = _Slot.header(B, scored, len(levels) if aligned else 0, compared)
+                total = expect[-1] if writer is not None else 0   # (scores / comparison only: the header is all that travels)
                 slot = slots[i % depth]   # (its previous batch, i - depth, has been finished: see the drain below)
                 ablock, worst, block = 0, 0, None
                 if aligned:
@@ -204,6 +246,9 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 keys = None
                 if scored:
                     _, keys = model.utterance_losses(out, cpu_batch, out=slot.dev[hdr - _COLS * B:hdr].view(B, _COLS))
+                if compared:
+                    at = hdr - _Slot.dtw_table(B)
+                    model.mel_dtw(out, ref, ref_lens, out=slot.dev[at:at + 2 * B])
                 if aligned:
                     tab = _Slot.table(B)
                     H.pack_rows([(rows[name], out["src_lens" if level == "phone" else "tgt_lens"],
@@ -220,7 +265,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                     copied_ev = torch.cuda.Event()
                     copied_ev.record(copy_stream)
                 slot.dev.record_stream(copy_stream)
-                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys, block))
+                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys, block, ref_frames))
                 # the next batch's forward is enqueued before this batch's copy is waited for: only what exceeds
                 # depth - 1 batches in flight is finished now
                 while len(pending) > depth - 1:
@@ -245,11 +290,17 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
 def collate_items(items: list, learn_alignment: bool, pin_memory: bool = False) -> dict:
     """``collate``'s batch of ``items``; when their style references are not all one object it also carries
     ``style_reference_lens`` (``data.style_reference_lens``: every reference's own frame count in the zero-padded
-    ``mel_style_reference``), which makes ``FastSpeech2.forward`` encode every row as if it were alone."""
+    ``mel_style_reference``), which makes ``FastSpeech2.forward`` encode every row as if it were alone.  Items of a
+    dataset with ``compare_dir`` carry ``compare_mel``: ``collate`` pads those to ``[B, Tr, n_mels]`` and ``compare_lens``
+    [B] int32 holds every recording's own frame count (both for ``FastSpeech2.mel_dtw``, neither for ``forward``)."""
     batch = collate(items, learn_alignment=learn_alignment, pin_memory=pin_memory)
     lens = style_reference_lens(items)
     if lens is not None:
         batch["style_reference_lens"] = lens
+    if "compare_mel" in items[0]:
+        # ``collate`` has padded the recordings to [B, Tr, n_mels]: their own frame counts travel beside them
+        batch["compare_lens"] = torch.tensor([len(item["compare_mel"]) for item in items], dtype=torch.int32,
+                                             pin_memory=pin_memory)
     return batch
 
 

@@ -720,6 +720,31 @@ int fs2hip_bn_act_bwd_lens(const float* dout, const float* y, const float* stats
                            float* coef, float* dgamma, float* dbeta, float* dy, int B, int H, int W, int C, int act,
                            void* stream);
 
+/* Dynamic time warping between two batches of frame sequences of different lengths (csrc/dtw.hip): the distance
+ * `fs2l synthesize --compare-to` reports between a free synthesis and the recorded mel.  Both calls are fp32, read the
+ * lengths from device memory (clamped to 0 .. T here), and use no host synchronisation, no atomics and no workspace.
+ *   frame_dist  a [B][T1][C], b [B][T2][C], cost [B][T1][T2].  With n = clamp(a_lens[u], 0, T1), r = clamp(b_lens[u], 0, T2):
+ *                   cost[u][i][j] = sqrtf(sum_c (a[u][i][c] - b[u][j][c])^2)      for i < n, j < r
+ *               in fp32 without contraction, c ascending from 0.f, the same for every element whatever the tiling.
+ *               Nothing else of cost is written; rows of a and b at and beyond the lengths are never read (they may hold
+ *               NaN).  C <= FS2_FRAME_DIST_MAX_C (the tiles' LDS), B <= 65535.
+ *   dtw         per utterance, on cost's n x r box: D[0][0] = c[0][0], S[0][0] = 1, and otherwise
+ *                   best = D[i-1][j-1]; if (D[i-1][j] < best) take (i-1, j); if (D[i][j-1] < best) take (i, j-1)
+ *                   D[i][j] = c[i][j] + best, S[i][j] = S[taken] + 1
+ *               with strict <, in that order, a predecessor that does not exist counting as +inf.  total[u] = D[n-1][r-1],
+ *               steps[u] = S[n-1][r-1] = the cells on the path a backtrack under the same rule finds; (0.f, 0) when n or r
+ *               is 0.  Adds and compares only: bit-exact from cost, and a row does not depend on the rest of the batch.
+ *               total and steps are written for every u; nothing outside the box is read.  One wavefront per utterance,
+ *               64 columns at a time, ceil(r / 64) * (n + 63) dependent steps at most.  T1 <= FS2_DTW_MAX_T1 (8 bytes of LDS
+ *               per row beside the 16 KiB cost ring).
+ * FS2HIP_EINVAL, before any launch: a null pointer, a non-positive extent, an extent beyond the limits above. */
+#define FS2_FRAME_DIST_MAX_C 204
+#define FS2_DTW_MAX_T1 6144
+int fs2hip_frame_dist(const float* a, const int* a_lens, const float* b, const int* b_lens, float* cost, int B, int T1,
+                      int T2, int C, void* stream);
+int fs2hip_dtw(const float* cost, const int* lens1, const int* lens2, float* total, int* steps, int B, int T1, int T2,
+               void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
