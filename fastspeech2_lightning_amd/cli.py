@@ -184,6 +184,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "--exact-lengths).  Not with -T: teacher forcing fixes the lengths, --return-scores is its measure")
     sy.add_argument("--scores-only", action="store_true",
                     help="with --return-scores or --compare-to: write the score file and no spectrograms")
+    sy.add_argument("--write-paths", action="store_true",
+                    help="with --compare-to: also write OUTPUT_DIR/dtw_path/<basename>--...--dtw-path.pt, every row's warping path "
+                         "(per synthesized frame the recorded frames it is paired with and their distance) and what it says per "
+                         "token -- cells, distance and the token's boundaries in the recording -- and OUTPUT_DIR/dtw-tokens-<step>.psv, "
+                         "every row's worst token against its own mean, worst first (fs2hip_dtw_dirs + fs2hip_dtw_path; the rows "
+                         "leave the GPU in the copy that carries the spectrograms)")
     sy.add_argument("--write-alignments", action="store_true",
                     help="also write OUTPUT_DIR/synthesized_alignment/*--alignment.pt: every text's tokens, per-token durations in "
                          "frames, and the pitch and energy predictions (a dict of tensors; fs2hip_pack_rows packs them into the "
@@ -827,9 +833,11 @@ def synthesize_command(args) -> int:
     if args.compare_to is not None and args.texts:
         raise SystemExit("--compare-to needs --filelist (-f): the recorded mel of a row is found by its basename, and a --text "
                          "(-t) has none")
+    if args.write_paths and args.compare_to is None:
+        raise SystemExit("--write-paths goes with --compare-to: the path is the one that leads to the recording")
     if args.scores_only and not (args.return_scores or args.compare_to is not None):
         raise SystemExit("--scores-only goes with --return-scores or --compare-to")
-    from .data import (AlignmentWriter, DtwWriter, PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores,
+    from .data import (AlignmentWriter, DtwPathWriter, DtwWriter, PackedSpecWriter, ScoreWriter, SynthesisDataset, coverage_scores,
                        synthesis_batches, synthesis_entries)
     print(f"Loading checkpoint from {args.model_path}", file=sys.stderr)
     if args.dry_run:
@@ -873,6 +881,11 @@ def synthesize_command(args) -> int:
         if compare is not None:
             plan["compare_to"] = str(args.compare_to)
             plan["dtw_file"] = str(compare.path)
+            if args.write_paths:
+                paths = DtwPathWriter(args.output_dir, global_step, dataset.text_processor.symbols)
+                plan["dtw_tokens_file"] = str(paths.path)
+                plan["path_files"] = [str(paths.filename(e["basename"], e.get("speaker") or "default",
+                                                                e.get("language") or "default")) for e in entries]
         if args.write_alignments:
             plan["alignment_files"] = alignment_file_names(dataset, args.output_dir, global_step)
             if dataset.teacher_forcing and config.model.learn_alignment:
@@ -889,10 +902,11 @@ def synthesize_command(args) -> int:
     alignments = None
     if args.write_alignments:
         alignments = AlignmentWriter(args.output_dir, global_step, dataset.text_processor.symbols)
+    paths = DtwPathWriter(args.output_dir, global_step, dataset.text_processor.symbols) if args.write_paths else None
     control = InferenceControl(pitch=args.pitch_control, energy=args.energy_control, duration=args.duration_control)
     t0 = time.perf_counter()
     res = synthesize(model, dataset, args.batch_size, control, writer, sort=sort, exact_lengths=args.exact_lengths,
-                     scores=scores, alignments=alignments, compare=compare)
+                     scores=scores, alignments=alignments, compare=compare, paths=paths)
     torch.cuda.synchronize()
     report = {"finished": True, "utterances": res["utterances"], "files": len(res["files"]), "frames": res["frames"],
               "batches": res["batches"], "seconds": round(time.perf_counter() - t0, 3),
@@ -901,6 +915,9 @@ def synthesize_command(args) -> int:
         report["scores_file"] = str(scores.close())
     if compare is not None:
         report["dtw_file"] = str(compare.close())
+    if paths is not None:
+        report["path_files"] = len(res["path_files"])
+        report["dtw_tokens_file"] = str(paths.close())
     if alignments is not None:
         report["alignment_files"] = len(res["alignment_files"])
     print(json.dumps(report), flush=True)

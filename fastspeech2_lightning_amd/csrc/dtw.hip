@@ -5,6 +5,9 @@
 //   dtw        : D[0][0] = c[0][0], D[i][j] = c[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]) with the number of cells on
 //                the chosen path carried along; the minimum is taken in that order with strict <, so a tie keeps the
 //                diagonal, then the row above.  Adds and compares only: bit-exact from the cost matrix.
+//   dtw_dirs   : dtw that also writes the predecessor taken at every cell (0 diagonal, 1 up, 2 left)
+//   dtw_path   : the backtrack through those codes: per row of the box the first and last column on the path and the sum
+//                of the row's path cells, from the last column towards the first
 //
 // MAS (aligner.hip) reads the previous row only, so a wavefront can take a whole row per step.  Here a cell also needs
 // its LEFT neighbour of the same row: the cells of one anti-diagonal are what is independent.  One wavefront walks a
@@ -66,20 +69,28 @@ __global__ __launch_bounds__(256) void frame_dist_kernel(const float* __restrict
   }
 }
 
-// One wavefront per utterance.  LDS: ring[64][64] | colD[T1] | colS[T1].
+// One wavefront per utterance.  LDS: ring[64][64] | colD[T1] | colS[T1] | (DIRS) dring[64][64] bytes.
 //   ring  the strip's costs, a row per slot: lane t stores the 256-byte row segment's element t as the row arrives and reads
 //         it back t steps later (ring[(s - t) % 64][t]: bank t, conflict-free); the global loads behind it run DT_CH rows
 //         ahead in registers, so a step waits for LDS and never for memory.
 //   col   (D, S)[i] of the strip's last column, left by lane 63 for lane 0 of the next strip.  Lane 0 gets them back 64
 //         rows at a time (one read by all lanes, then a readlane per step); row i is read at step i and overwritten at
 //         step i + 63 of the same strip, so the column is updated in place.
+// DIRS: the predecessor taken at every cell is kept as well (0 diagonal, 1 up, 2 left; a byte per cell of dirs [B][T1][T2]).
+//   dring [64][64] bytes behind the columns, the mirror of `ring`: lane t drops the code of cell (i, j0 + t) into
+//         dring[i % 64][t]; at step s every lane of the strip is done with row s - (W - 1), and the wavefront stores that
+//         row's W codes as one contiguous segment before lane 0 takes the slot again 64 rows later.  Without the ring
+//         every step's byte stores would touch 64 different rows.
+template <bool DIRS>
 __global__ __launch_bounds__(64) void dtw_kernel(const float* __restrict__ cost, const int* __restrict__ lens1,
                                                  const int* __restrict__ lens2, float* __restrict__ total,
-                                                 int* __restrict__ steps, int T1, int T2) {
+                                                 int* __restrict__ steps, unsigned char* __restrict__ dirs, int T1,
+                                                 int T2) {
   extern __shared__ float sm[];
   float* ring = sm;
   float* colD = sm + DT_STRIP * DT_STRIP;
   int* colS = reinterpret_cast<int*>(colD + T1);
+  unsigned char* dring = reinterpret_cast<unsigned char*>(colS + T1);  // (DIRS only: the launch reserves it)
   const int u = blockIdx.x, lane = threadIdx.x;
   const int n = dt_clamp_len(lens1[u], T1), r = dt_clamp_len(lens2[u], T2);
   if (n == 0 || r == 0) {
@@ -90,6 +101,7 @@ __global__ __launch_bounds__(64) void dtw_kernel(const float* __restrict__ cost,
     return;
   }
   const float* cb = cost + (long long)u * T1 * T2;
+  unsigned char* db = DIRS ? dirs + (long long)u * T1 * T2 : nullptr;
   float upD = INFINITY;  // the lane's previous result: D / S of the cell above
   int upS = 0;
   int W = 0;
@@ -142,13 +154,16 @@ __global__ __launch_bounds__(64) void dtw_kernel(const float* __restrict__ cost,
           const int lfS = fs2_wave_shr1(upS, l0S);
           float best = dgD;
           int bs = dgS;
+          unsigned char code = 0;
           if (upD < best) {
             best = upD;
             bs = upS;
+            code = 1;
           }
           if (lfD < best) {
             best = lfD;
             bs = lfS;
+            code = 2;
           }
           dgD = lfD;
           dgS = lfS;
@@ -159,6 +174,13 @@ __global__ __launch_bounds__(64) void dtw_kernel(const float* __restrict__ cost,
               colD[i] = upD;
               colS[i] = upS;
             }
+            if constexpr (DIRS) dring[(i & 63) * DT_STRIP + lane] = code;
+          }
+          if constexpr (DIRS) {
+            // row s - (W - 1) is complete: lane t finished it at step s - (W - 1) + t <= s.  0 <= s - (W - 1) < n holds for
+            // every step from W - 1 on (s <= n + W - 2), so every row of the strip leaves exactly once
+            const int done = s - (W - 1);
+            if (done >= 0 && col_ok) db[(long long)done * T2 + jl] = dring[(done & 63) * DT_STRIP + lane];
           }
           c = cnext;
         }
@@ -169,6 +191,66 @@ __global__ __launch_bounds__(64) void dtw_kernel(const float* __restrict__ cost,
   if (lane == W - 1) {
     total[u] = upD;
     steps[u] = upS;
+  }
+}
+
+// The backtrack through `dirs`, one wavefront per utterance.  The walk is a chain of dependent reads, so it runs out of
+// LDS: the wavefront fetches the DP_ROWS x 64 tile of codes and costs whose lower right corner is the walk's cell (a lane
+// per column, every load of the tile in flight at once), then follows the path through the tile -- at least DP_ROWS moves
+// -- before it pays a memory latency again.  All lanes walk together (uniform reads: LDS broadcasts), lane 0 writes a row's
+// three results when the walk leaves the row.  A code the recursion cannot have written (dirs is the caller's memory)
+// cannot lead outside the box: column 0 only goes up, row 0 only goes left, anything but 1 and 2 is a diagonal.
+constexpr int DP_ROWS = 32;
+
+__global__ __launch_bounds__(64) void dtw_path_kernel(const float* __restrict__ cost, const unsigned char* __restrict__ dirs,
+                                                      const int* __restrict__ lens1, const int* __restrict__ lens2,
+                                                      int* __restrict__ ref_first, int* __restrict__ ref_last,
+                                                      float* __restrict__ frame_cost, int T1, int T2) {
+  __shared__ float ct[DP_ROWS * DT_STRIP];
+  __shared__ unsigned char dt[DP_ROWS * DT_STRIP];
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int n = dt_clamp_len(lens1[u], T1), r = dt_clamp_len(lens2[u], T2);
+  if (n == 0 || r == 0) return;
+  const float* cb = cost + (long long)u * T1 * T2;
+  const unsigned char* db = dirs + (long long)u * T1 * T2;
+  const long long ob = (long long)u * T1;
+  int i = n - 1, j = r - 1, last = j;
+  float fc = 0.f;
+  bool fresh = true;  // the walk has just entered row i: its sum starts from this cell's cost
+  for (;;) {
+    const int i0 = max(i - (DP_ROWS - 1), 0), j0 = max(j - (DT_STRIP - 1), 0);  // the tile: rows i0 .. i, columns j0 .. j
+    __syncthreads();
+    if (j0 + lane <= j) {
+      for (int k = 0; k <= i - i0; ++k) {
+        const long long at = (long long)(i0 + k) * T2 + j0 + lane;
+        ct[k * DT_STRIP + lane] = cb[at];
+        dt[k * DT_STRIP + lane] = db[at];
+      }
+    }
+    __syncthreads();
+    while (i >= i0 && j >= j0) {
+      const int at = (i - i0) * DT_STRIP + (j - j0);
+      const float c = ct[at];
+      int d = __builtin_amdgcn_readfirstlane((int)dt[at]);
+      fc = fresh ? c : fc + c;
+      fresh = false;
+      if (j == 0) d = 1;
+      else if (i == 0) d = 2;
+      if (d == 2) {
+        --j;
+        continue;
+      }
+      if (lane == 0) {
+        ref_first[ob + i] = j;
+        ref_last[ob + i] = last;
+        frame_cost[ob + i] = fc;
+      }
+      if (i == 0) return;  // (0, 0): the path is complete
+      --i;
+      if (d != 1) --j;
+      last = j;
+      fresh = true;
+    }
   }
 }
 
@@ -190,7 +272,27 @@ extern "C" int fs2hip_dtw(const float* cost, const int* lens1, const int* lens2,
   if (!cost || !lens1 || !lens2 || !total || !steps || B <= 0 || T1 <= 0 || T2 <= 0) return FS2HIP_EINVAL;
   if (T1 > FS2_DTW_MAX_T1) return FS2HIP_EINVAL;
   const size_t smem = (size_t)(DT_STRIP * DT_STRIP + 2 * (size_t)T1) * sizeof(float);
-  dtw_kernel<<<dim3(B), dim3(64), smem, (hipStream_t)stream>>>(cost, lens1, lens2, total, steps, T1, T2);
+  dtw_kernel<false><<<dim3(B), dim3(64), smem, (hipStream_t)stream>>>(cost, lens1, lens2, total, steps, nullptr, T1, T2);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_dtw_dirs(const float* cost, const int* lens1, const int* lens2, float* total, int* steps,
+                               unsigned char* dirs, int B, int T1, int T2, void* stream) {
+  if (!cost || !lens1 || !lens2 || !total || !steps || !dirs || B <= 0 || T1 <= 0 || T2 <= 0) return FS2HIP_EINVAL;
+  if (T1 > FS2_DTW_PATH_MAX_T1) return FS2HIP_EINVAL;
+  const size_t smem = (size_t)(DT_STRIP * DT_STRIP + 2 * (size_t)T1) * sizeof(float) + DT_STRIP * DT_STRIP;
+  dtw_kernel<true><<<dim3(B), dim3(64), smem, (hipStream_t)stream>>>(cost, lens1, lens2, total, steps, dirs, T1, T2);
+  FS2_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int fs2hip_dtw_path(const float* cost, const unsigned char* dirs, const int* lens1, const int* lens2,
+                               int* ref_first, int* ref_last, float* frame_cost, int B, int T1, int T2, void* stream) {
+  if (!cost || !dirs || !lens1 || !lens2 || !ref_first || !ref_last || !frame_cost || B <= 0 || T1 <= 0 || T2 <= 0)
+    return FS2HIP_EINVAL;
+  dtw_path_kernel<<<dim3(B), dim3(64), 0, (hipStream_t)stream>>>(cost, dirs, lens1, lens2, ref_first, ref_last, frame_cost,
+                                                                 T1, T2);
   FS2_LAUNCH_CHECK();
   return 0;
 }

@@ -742,6 +742,215 @@ class DtwWriter:
         return self.path
 
 
+class DtwPathWriter:
+    """Where free synthesis is far from the recording: the warping path of ``FastSpeech2.mel_dtw_paths`` cut
+    into the model's own tokens, one ``.pt`` file per dataset entry under the FILELIST's basename (as ``DtwWriter``'s rows
+    are):
+
+        ``OUT/dtw_path/<basename>--<speaker>--<language>--ckpt=<step>--dtw-path.pt``
+
+    a dict of tensors, numbers, strings and lists of strings (``torch.load(..., weights_only=True)`` reads it):
+
+    * per synthesized frame ``i``: ``ref_first`` / ``ref_last`` int32 [frames], the first and last recorded frame the path
+      pairs it with, and ``frame_cost`` fp32 [frames], the sum of those pairs' distances (``fs2hip_dtw_path``);
+    * ``frames``, ``ref_frames``, ``total``, ``steps``: as in ``dtw-<step>.psv``;
+    * ``text`` int32 [n], ``symbols`` (n strings), ``duration`` int32 [n]: the durations as rendered -- through
+      ``AlignmentWriter.clip`` when the model's ``max_length`` cut the output -- so they add up to ``frames``;
+    * per token ``k``, which owns frames ``[s_k, e_k)`` of the cumulative durations: ``token_cells`` int64 [n] = the sum of
+      ``ref_last[i] - ref_first[i] + 1`` over its frames, ``token_cost`` float64 [n] = the sum of their ``frame_cost``
+      (exactly rounded, ``math.fsum``: no summation order to agree on), ``token_ref_start`` = ``ref_first[s_k]`` and
+      ``token_ref_end`` = ``ref_last[e_k - 1] + 1`` (exclusive), int32 [n]: the token's boundaries in the RECORDING.  A token
+      without frames has 0 cells, 0 cost, and start = end = the start of the next token that has frames
+      (``ref_frames`` when there is none).  Two neighbouring tokens may share one recorded frame: when the path goes up
+      across their boundary, the last frame of one and the first frame of the next are paired with the same recorded
+      frame, so ``token_ref_end[k] = token_ref_start[k + 1] + 1`` and ``token_cells`` adds up to ``steps``, not to
+      ``ref_frames``;
+    * ``basename``, ``speaker``, ``language``, ``raw_text``.
+
+    An entry without a path (no frames on either side: ``steps == 0``) gets empty per-frame tensors and tokens without
+    cells.  What must hold for a path is checked, ``ValueError`` otherwise: ``ref_first[0] == 0``, ``ref_last[-1] ==
+    ref_frames - 1``, ``ref_first[i]`` is ``ref_last[i-1]`` or ``ref_last[i-1] + 1``, ``ref_first <= ref_last``, and the
+    cells add up to ``steps``.
+
+    ``close()`` writes ``OUT/dtw-tokens-<step>.psv``, one '|'-separated row per entry: its worst token -- the largest
+    ``token_cost / token_cells`` over tokens with cells (the first of equals), ``token_mel_dtw`` -- beside the entry's
+    own mean ``mel_dtw = total / steps`` and their quotient ``ratio``.  Rows are sorted by ``-ratio``, entries without
+    one (no path, or a mean of 0) last, ties in input order.
+
+    ``write_packed`` takes a batch's packed HOST buffer (fp32; int32 members are read through a view) and the members'
+    places in it; every piece is cloned out of the buffer (the caller reuses it)."""
+
+    MEMBERS = ("duration", "ref_first", "ref_last", "frame_cost")
+    FIELDS = ("basename", "speaker", "language", "token_index", "symbol", "token_frames", "ref_start", "ref_end",
+              "token_mel_dtw", "mel_dtw", "ratio", "raw_text")
+
+    def __init__(self, out_dir, global_step: int = 0, symbols=None):
+        self.out_dir = Path(out_dir)
+        self.dir = self.out_dir / "dtw_path"
+        self.global_step = int(global_step)
+        table = getattr(symbols, "symbols", symbols)
+        if table is None:
+            raise ValueError("DtwPathWriter: the model's symbol table is required (TextProcessor(config.text).symbols)")
+        self.symbols = list(table)
+        self.records = {}
+
+    @property
+    def path(self) -> Path:
+        return self.out_dir / f"dtw-tokens-{self.global_step}.psv"
+
+    def filename(self, basename, speaker, language) -> Path:
+        return self.dir / SEP.join([basename, speaker, language, f"ckpt={self.global_step}", "dtw-path.pt"])
+
+    @staticmethod
+    def tokens(duration, ref_first, ref_last, frame_cost, ref_frames: int) -> dict:
+        """The per-token values of the class docstring from one utterance's (clipped) durations and per-frame path."""
+        import math
+        dur = duration.to(torch.int64)
+        ends = dur.cumsum(0).tolist()
+        n = len(ends)
+        span = (ref_last.to(torch.int64) - ref_first.to(torch.int64) + 1).cumsum(0).tolist()
+        first, last, costs = ref_first.tolist(), ref_last.tolist(), frame_cost.tolist()
+        cells, cost, start, end = [0] * n, [0.0] * n, [0] * n, [0] * n
+        nxt = int(ref_frames)
+        for k in range(n - 1, -1, -1):
+            e = ends[k]
+            s = ends[k - 1] if k else 0
+            if e > s:
+                cells[k] = span[e - 1] - (span[s - 1] if s else 0)
+                cost[k] = math.fsum(costs[s:e])
+                start[k], end[k] = first[s], last[e - 1] + 1
+                nxt = start[k]
+            else:
+                start[k] = end[k] = nxt
+        return {"token_cells": torch.tensor(cells, dtype=torch.int64), "token_cost": torch.tensor(cost, dtype=torch.float64),
+                "token_ref_start": torch.tensor(start, dtype=torch.int32), "token_ref_end": torch.tensor(end, dtype=torch.int32)}
+
+    @staticmethod
+    def check(name, ref_first, ref_last, ref_frames: int, steps: int):
+        """Raises ``ValueError`` unless the per-frame rows describe one monotone path over all ``ref_frames`` recorded
+        frames with ``steps`` cells."""
+        first, last = ref_first.to(torch.int64), ref_last.to(torch.int64)
+        if first.numel() == 0:
+            raise ValueError(f"DtwPathWriter: {name!r} has no frames, but the recursion counted {steps} cells")
+        if int(first[0]) != 0 or int(last[-1]) != ref_frames - 1:
+            raise ValueError(f"DtwPathWriter: the path of {name!r} runs from recorded frame {int(first[0])} to "
+                             f"{int(last[-1])}, not from 0 to {ref_frames - 1}")
+        if bool((first > last).any()):
+            raise ValueError(f"DtwPathWriter: the path of {name!r} has a frame whose first recorded frame lies behind its last")
+        step = first[1:] - last[:-1]
+        if bool(((step != 0) & (step != 1)).any()):
+            i = int(torch.nonzero((step != 0) & (step != 1))[0]) + 1
+            raise ValueError(f"DtwPathWriter: the path of {name!r} is not connected at frame {i}: it starts at recorded frame "
+                             f"{int(first[i])} where frame {i - 1} ended at {int(last[i - 1])}")
+        cells = int((last - first + 1).sum())
+        if cells != steps:
+            raise ValueError(f"DtwPathWriter: the path of {name!r} has {cells} cells where the recursion counted {steps}")
+
+    def write_packed(self, packed: torch.Tensor, members: dict, batch: dict, positions, frames, ref_frames, totals,
+                     steps) -> list[Path]:
+        """``members``: ``{"duration" | "ref_first" | "ref_last" | "frame_cost": (start, offsets)}`` -- the member's first
+        element in ``packed`` and its B + 1 element offsets from there (``hip.pack_rows``'s): ``duration`` per token, the
+        others per synthesized frame.  ``frames`` / ``ref_frames`` / ``totals`` / ``steps``: every utterance's frame count
+        in the written spectrogram, in its recording, and its DTW total and cell count."""
+        if sorted(members) != sorted(self.MEMBERS):
+            raise ValueError(f"DtwPathWriter: members must be {', '.join(self.MEMBERS)}, got {sorted(members)}")
+        B = len(positions)
+        for what, values in (("frame counts", frames), ("recorded frame counts", ref_frames), ("totals", totals),
+                             ("step counts", steps)):
+            if len(values) != B:
+                raise ValueError(f"DtwPathWriter: {len(values)} {what} for {B} utterances")
+        table = {}
+        for name, (start, offsets) in members.items():
+            offsets = [int(o) for o in offsets]
+            if len(offsets) != B + 1:
+                raise ValueError(f"DtwPathWriter: {len(offsets)} {name} offsets for {B} utterances")
+            if offsets[0] != 0 or any(b < a for a, b in zip(offsets, offsets[1:])) or start < 0 \
+                    or start + offsets[-1] > packed.numel():
+                raise ValueError(f"DtwPathWriter: the {name} offsets {offsets} from element {start} do not delimit rows of a "
+                                 f"buffer of {packed.numel()} elements")
+            table[name] = (int(start), offsets)
+        ints = packed.view(torch.int32)
+        written = []
+        for i, pos in enumerate(positions):
+            pos = int(pos)
+            if pos in self.records:
+                raise ValueError(f"DtwPathWriter: position {pos} delivered twice")
+            name, n_frames, n_ref, n_steps = batch["basename"][i], int(frames[i]), int(ref_frames[i]), int(steps[i])
+
+            def piece(member, source):
+                start, off = table[member]
+                return source[start + off[i]:start + off[i + 1]].clone()
+
+            dur = piece("duration", ints)
+            summed = int(dur.sum())
+            if n_frames > summed or n_frames < 0:
+                raise ValueError(f"DtwPathWriter: utterance {name!r} has {n_frames} frames but durations that add up to {summed}")
+            if summed != n_frames:
+                dur = AlignmentWriter.clip(dur, n_frames)
+            text = torch.as_tensor(batch["text"][i]).reshape(-1)
+            if text.numel() < dur.numel():
+                raise ValueError(f"DtwPathWriter: utterance {name!r} has {dur.numel()} durations for {text.numel()} tokens")
+            text = text[:dur.numel()].to(torch.int32).clone()
+            first, last, cost = piece("ref_first", ints), piece("ref_last", ints), piece("frame_cost", packed)
+            for member, t in (("ref_first", first), ("ref_last", last), ("frame_cost", cost)):
+                if t.numel() != n_frames:
+                    raise ValueError(f"DtwPathWriter: utterance {name!r}: {t.numel()} {member} values for {n_frames} frames")
+            owned = dur
+            if n_steps > 0:
+                self.check(name, first, last, n_ref, n_steps)
+            else:   # no frames on one side: nothing of the path is defined, and no token owns a piece of it
+                first, last, cost, owned = first[:0], last[:0], cost[:0], torch.zeros_like(dur)
+            tokens = self.tokens(owned, first, last, cost, n_ref)
+            symbols = [self.symbols[t] for t in text.tolist()]
+            speaker, language, raw_text = batch["speaker"][i], batch["language"][i], batch["raw_text"][i]
+            record = {"ref_first": first, "ref_last": last, "frame_cost": cost, "frames": n_frames, "ref_frames": n_ref,
+                      "total": float(totals[i]), "steps": n_steps, "text": text, "symbols": symbols, "duration": dur,
+                      **tokens, "basename": name, "speaker": speaker, "language": language, "raw_text": raw_text}
+            path = self.filename(name, speaker, language)
+            path.parent.mkdir(parents=True, exist_ok=True)
+            torch.save(record, path)
+            written.append(path)
+            self.records[pos] = self.worst_token(record)
+        return written
+
+    @staticmethod
+    def worst_token(record: dict) -> dict:
+        """The entry's row of ``dtw-tokens-<step>.psv``."""
+        row = {k: record[k] for k in ("basename", "speaker", "language", "raw_text")}
+        row.update(token_index=None, symbol=None, token_frames=None, ref_start=None, ref_end=None, token_mel_dtw=None,
+                   ratio=None)
+        row["mel_dtw"] = record["total"] / record["steps"] if record["steps"] > 0 else None
+        cells, cost = record["token_cells"].tolist(), record["token_cost"].tolist()
+        best = None
+        for k, (n, c) in enumerate(zip(cells, cost)):
+            if n > 0 and (best is None or c / n > best[0]):
+                best = (c / n, k)
+        if best is not None:
+            k = best[1]
+            row.update(token_index=k, symbol=record["symbols"][k], token_frames=int(record["duration"][k]),
+                       ref_start=int(record["token_ref_start"][k]), ref_end=int(record["token_ref_end"][k]),
+                       token_mel_dtw=best[0])
+            if row["mel_dtw"]:
+                row["ratio"] = best[0] / row["mel_dtw"]
+        return row
+
+    def sorted_records(self) -> list[dict]:
+        rows = [self.records[p] for p in sorted(self.records)]
+        rows.sort(key=lambda r: (r["ratio"] is None, -r["ratio"] if r["ratio"] is not None else 0.0))
+        return rows
+
+    def close(self) -> Path:
+        import csv
+        self.out_dir.mkdir(parents=True, exist_ok=True)
+        with open(self.path, "w", encoding="utf8", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=list(self.FIELDS), delimiter="|", restval="", extrasaction="ignore",
+                               lineterminator="\n")
+            w.writeheader()
+            for r in self.sorted_records():
+                w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in r.items() if v is not None})
+        return self.path
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # synthesis: text -> inference items -> batches (reference fs2/cli/synthesize.py:136-319, fs2/dataset.py:88-224)
 # ----------------------------------------------------------------------------------------------------------------------

@@ -163,6 +163,8 @@ SIGNATURES = {
     "fs2hip_bn_act_bwd_lens": "pppppppppiiiiip",
     "fs2hip_frame_dist": "pppppiiiip",
     "fs2hip_dtw": "pppppiiip",
+    "fs2hip_dtw_dirs": "ppppppiiip",
+    "fs2hip_dtw_path": "pppppppiiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -2293,25 +2295,77 @@ def frame_dist(a, a_lens, b, b_lens, out=None):
     return out
 
 
+DTW_PATH_MAX_T1 = 5632  # FS2_DTW_PATH_MAX_T1
+
+
 def dtw(cost, lens1, lens2, total=None, steps=None):
     """(total [B] fp32, steps [B] int32): the accumulated cost of the cheapest monotone path through every utterance's
     ``lens1[u] x lens2[u]`` box of ``cost`` [B, T1, T2] and the number of cells on it -- diagonal, then up, then left,
     each taken only when strictly cheaper (``fs2hip_dtw``; include/fs2hip.h has the recursion).  An empty box gives (0,
     0).  Bit-exact from ``cost``; one wavefront per utterance."""
-    _chk(cost, name="dtw: cost")
-    _req(cost.dim() == 3 and cost.numel() > 0, f"dtw: cost {tuple(cost.shape)} is not a non-empty [B, T1, T2]")
+    return _dtw("dtw", cost, lens1, lens2, total, steps, None)
+
+
+def dtw_dirs(cost, lens1, lens2, dirs, total=None, steps=None):
+    """``dtw`` that also keeps the path: (total, steps), the same bit for bit, and in ``dirs`` [B, T1, T2] uint8 the
+    predecessor taken at every cell of each box, one byte per cell -- 0 diagonal, 1 up ``(i-1, j)``, 2 left ``(i, j-1)``
+    (``fs2hip_dtw_dirs``; what ``dtw_path`` walks back through).  Bytes outside a box are left as they are.  ``T1`` is at
+    most ``DTW_PATH_MAX_T1``: the codes leave through a second LDS ring."""
+    _chk(dirs, torch.uint8, "dtw_dirs: dirs")
+    return _dtw("dtw_dirs", cost, lens1, lens2, total, steps, dirs)
+
+
+def _dtw(what, cost, lens1, lens2, total, steps, dirs):
+    _chk(cost, name=f"{what}: cost")
+    _req(cost.dim() == 3 and cost.numel() > 0, f"{what}: cost {tuple(cost.shape)} is not a non-empty [B, T1, T2]")
     B, T1, T2 = cost.shape
-    _req(T1 <= DTW_MAX_T1, f"dtw: T1 = {T1}: at most {DTW_MAX_T1} rows (8 bytes of LDS per row beside the cost ring)")
-    _dtw_lens("dtw", lens1, lens2, B)
+    if dirs is None:
+        _req(T1 <= DTW_MAX_T1, f"{what}: T1 = {T1}: at most {DTW_MAX_T1} rows (8 bytes of LDS per row beside the cost ring)")
+    else:
+        _req(T1 <= DTW_PATH_MAX_T1, f"{what}: T1 = {T1}: at most {DTW_PATH_MAX_T1} rows (8 bytes of LDS per row beside the "
+                                    "cost ring and the ring of codes)")
+        _req(tuple(dirs.shape) == (B, T1, T2), f"{what}: dirs is {tuple(dirs.shape)}, expected {(B, T1, T2)}")
+    _dtw_lens(what, lens1, lens2, B)
     if total is None:
         total = torch.empty(B, device=cost.device, dtype=torch.float32)
     if steps is None:
         steps = torch.empty(B, device=cost.device, dtype=torch.int32)
-    _chk(total, name="dtw: total"); _chk(steps, torch.int32, "dtw: steps")
+    _chk(total, name=f"{what}: total"); _chk(steps, torch.int32, f"{what}: steps")
     _req(total.numel() == B and steps.numel() == B,
-         f"dtw: total has {total.numel()} and steps {steps.numel()} entries for {B} utterances")
-    _ok(lib().fs2hip_dtw(_p(cost), _p(lens1), _p(lens2), _p(total), _p(steps), B, T1, T2, _stream()), "dtw")
+         f"{what}: total has {total.numel()} and steps {steps.numel()} entries for {B} utterances")
+    if dirs is None:
+        _ok(lib().fs2hip_dtw(_p(cost), _p(lens1), _p(lens2), _p(total), _p(steps), B, T1, T2, _stream()), what)
+    else:
+        _ok(lib().fs2hip_dtw_dirs(_p(cost), _p(lens1), _p(lens2), _p(total), _p(steps), _p(dirs), B, T1, T2, _stream()), what)
     return total, steps
+
+
+def dtw_path(cost, dirs, lens1, lens2, ref_first=None, ref_last=None, frame_cost=None):
+    """(ref_first [B, T1] int32, ref_last [B, T1] int32, frame_cost [B, T1] fp32): the warping path ``dtw_dirs(..., dirs)``
+    chose, walked back from ``(n-1, r-1)`` to ``(0, 0)`` (``fs2hip_dtw_path``).  For every row ``i < lens1[u]``:
+    the smallest and largest column of the path's cells in that row, and the sum of their costs -- fp32, starting from
+    ``cost[i, ref_last]`` and adding towards ``ref_first``, so it is bit-defined.  Rows at and beyond ``lens1[u]`` and the
+    rows of an empty box are left as they are (tensors allocated here are ``torch.empty``).  One wavefront per
+    utterance; nothing is read back."""
+    _chk(cost, name="dtw_path: cost")
+    _req(cost.dim() == 3 and cost.numel() > 0, f"dtw_path: cost {tuple(cost.shape)} is not a non-empty [B, T1, T2]")
+    B, T1, T2 = cost.shape
+    _chk(dirs, torch.uint8, "dtw_path: dirs")
+    _req(tuple(dirs.shape) == (B, T1, T2), f"dtw_path: dirs is {tuple(dirs.shape)}, expected {(B, T1, T2)}")
+    _dtw_lens("dtw_path", lens1, lens2, B)
+    if ref_first is None:
+        ref_first = torch.empty(B, T1, device=cost.device, dtype=torch.int32)
+    if ref_last is None:
+        ref_last = torch.empty(B, T1, device=cost.device, dtype=torch.int32)
+    if frame_cost is None:
+        frame_cost = torch.empty(B, T1, device=cost.device, dtype=torch.float32)
+    _chk(ref_first, torch.int32, "dtw_path: ref_first"); _chk(ref_last, torch.int32, "dtw_path: ref_last")
+    _chk(frame_cost, name="dtw_path: frame_cost")
+    for name, t in (("ref_first", ref_first), ("ref_last", ref_last), ("frame_cost", frame_cost)):
+        _req(tuple(t.shape) == (B, T1), f"dtw_path: {name} is {tuple(t.shape)}, expected {(B, T1)}")
+    _ok(lib().fs2hip_dtw_path(_p(cost), _p(dirs), _p(lens1), _p(lens2), _p(ref_first), _p(ref_last), _p(frame_cost), B, T1,
+                              T2, _stream()), "dtw_path")
+    return ref_first, ref_last, frame_cost
 
 
 def duration_cumsum(dur, Tm, expect=None, bad_count=None):

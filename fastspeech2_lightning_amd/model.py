@@ -1409,6 +1409,19 @@ class FastSpeech2(_Base):
         nothing is read back.  ``out``: a ``2 * B`` fp32 device vector to fill instead of fresh tensors -- the totals, then
         the step counts as int32 bit patterns (``synthesize`` hands in a piece of the buffer that leaves the GPU with the
         spectrograms).  The cost matrices live in a persistent buffer that only grows."""
+        return self._mel_dtw(output, ref, ref_lens, out, False)
+
+    def mel_dtw_paths(self, output, ref, ref_lens, out=None):
+        """``mel_dtw`` with the warping path itself: ``(total, steps, ref_first, ref_last, frame_cost)``.  ``total``,
+        ``steps`` and ``out`` are ``mel_dtw``'s, bit for bit; the last three are ``[B, Tm]`` (int32, int32, fp32) -- for
+        every synthesized frame ``i < tgt_lens[b]`` the first and last recorded frame the path pairs it with and the sum of
+        those pairs' distances (``hip.dtw_dirs`` + ``hip.dtw_path``; include/fs2hip.h has the codes and the summation
+        order).  Rows beyond an utterance's frames, and all rows of an utterance without frames on either side, are not
+        written.  The directions, a byte per cell, live in a second grow-only persistent buffer beside the cost
+        matrices; ``Tm`` is at most ``hip.DTW_PATH_MAX_T1``.  Three launches, nothing is read back."""
+        return self._mel_dtw(output, ref, ref_lens, out, True)
+
+    def _mel_dtw(self, output, ref, ref_lens, out, paths):
         if self.training:
             raise ValueError("mel_dtw needs a model in eval mode (model.eval()): the distance is an inference result")
         y, lens = output.get(self.output_key), output.get("tgt_lens")
@@ -1433,10 +1446,19 @@ class FastSpeech2(_Base):
             if Tr == 0 or Tm == 0:   # nothing recorded (or synthesized) in the whole batch
                 total = H.zeros(B, device=y.device) if total is None else total.zero_()
                 steps = H.zeros(B, device=y.device, dtype=torch.int32) if steps is None else steps.zero_()
+                if paths:
+                    rows = max(Tm, 1)   # (no box has a cell: nothing of these is ever defined)
+                    return (total, steps, torch.empty(B, rows, device=y.device, dtype=torch.int32),
+                            torch.empty(B, rows, device=y.device, dtype=torch.int32),
+                            torch.empty(B, rows, device=y.device, dtype=torch.float32))
                 return total, steps
             cost = H.persistent_buffer("mel_dtw_cost", torch.float32, B * Tm * Tr)[:B * Tm * Tr].view(B, Tm, Tr)
             H.frame_dist(y.contiguous(), lens, ref, ref_lens, out=cost)
-            return H.dtw(cost, lens, ref_lens, total=total, steps=steps)
+            if not paths:
+                return H.dtw(cost, lens, ref_lens, total=total, steps=steps)
+            dirs = H.persistent_buffer("mel_dtw_dirs", torch.uint8, B * Tm * Tr)[:B * Tm * Tr].view(B, Tm, Tr)
+            total, steps = H.dtw_dirs(cost, lens, ref_lens, dirs, total=total, steps=steps)
+            return (total, steps) + H.dtw_path(cost, dirs, lens, ref_lens)
 
     def configure_optimizers(self):
         """fs2/model.py:530-549: ``([AdamW], [{"scheduler": NoamLR, "interval": "step"}])`` -- here a

@@ -47,6 +47,15 @@ recording -- ``B`` totals and ``B`` step counts -- where the score table would b
 never occur together: scores need teacher forcing, which fixes the lengths and makes warping pointless).  So the batch
 still leaves in the one copy and is waited for once.  ``exact_lengths`` is forced on, as for scores.  The unit is the
 dataset entry, i.e. the filelist row.  Without ``compare`` not one launch, allocation or header byte changes.
+
+``paths`` (a ``data.DtwPathWriter``, only with ``compare``; ``fs2l synthesize --compare-to DIR --write-paths``) adds WHERE an
+utterance is far from its recording: ``FastSpeech2.mel_dtw_paths`` also walks the warping path back, and ONE
+more ``hip.pack_rows`` call cuts four members to every utterance's own lengths into a path block behind the alignment
+block -- ``duration_rounded`` by ``src_lens``, and per synthesized frame the first and last recorded frame the path pairs it
+with and the sum of those pairs' distances, by ``tgt_lens``.  The block follows the alignment block's rules: its own offset
+tables in the header (behind the alignment block's), sizes from lengths the host already has, 16-byte alignment, the
+device's offsets checked against the host's, and the batch still leaves in the one copy and is waited for once.  The DTW
+totals stay where they are.  Without ``paths`` not one launch, allocation or header byte changes.
 """
 from __future__ import annotations
 
@@ -60,12 +69,14 @@ from .model import LOSS_KEYS
 
 
 class _Slot:
-    """One device buffer + its pinned host twin, both float32: [header | alignment block | payload].  The header holds the
-    batch's B + 1 int64 offsets (2 floats each, rounded up to 4 floats so that what follows starts 16-byte aligned), then
-    -- when alignments are written -- one such table per member of the alignment block, and, when the batch is scored,
+    """One device buffer + its pinned host twin, both float32: [header | alignment block | path block | payload].  The header
+    holds the batch's B + 1 int64 offsets (2 floats each, rounded up to 4 floats so that what follows starts 16-byte
+    aligned), then -- when alignments are written -- one such table per member of the alignment block, then -- when warping
+    paths are written -- one per member of the path block, and, when the batch is scored,
     its [B, 8] table of per-utterance losses last -- or, when the batch is compared to recordings, its B DTW totals and B
-    step counts there instead.  The alignment block (only with alignments) holds the members' packed
-    rows back to back and is rounded up to 4 floats, so the payload starts 16-byte aligned with or without it."""
+    step counts there instead.  The alignment block (only with alignments) and the path block (only with paths) each hold
+    their members' packed rows back to back and are rounded up to 4 floats, so the payload starts 16-byte aligned with or
+    without them."""
 
     def __init__(self, device):
         self.device, self.dev, self.host = device, None, None
@@ -94,7 +105,7 @@ _COLS = len(LOSS_KEYS) + 1   # columns of the score table: the loss terms and th
 
 
 def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort: bool = True, depth: int = 2,
-               exact_lengths: bool = False, scores=None, alignments=None, compare=None) -> dict:
+               exact_lengths: bool = False, scores=None, alignments=None, compare=None, paths=None) -> dict:
     """Synthesizes every item of ``dataset`` (``data.SynthesisDataset``) and writes the spectrograms through ``writer``
     (``data.PackedSpecWriter``), in input order.  Returns ``{"files": [paths], "utterances": n, "frames": n, "batches": n}``.
     Per batch the host reads the GPU once inside the forward pass (the frame totals; nothing for a teacher-forced batch)
@@ -106,14 +117,20 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
     ``writer`` may be None here too.  ``compare`` (``data.DtwWriter``): every entry's DTW distance between its free
     synthesis and its recorded mel is added to it (the caller closes it); the dataset must carry the recordings
     (``SynthesisDataset(..., compare_dir=...)``, so it is not teacher-forced), ``exact_lengths`` is forced on, and
-    ``writer`` may be None (comparison only).  At least one of the four is required."""
+    ``writer`` may be None (comparison only).  ``paths`` (``data.DtwPathWriter``, only together with ``compare``): every
+    entry's warping path and per-token distances are written through it (the result gains ``"path_files"``; the caller
+    closes it, which writes the per-token table).  At least one of writer, scores, alignments and compare is required."""
     if depth < 1:
         raise ValueError("synthesize: depth >= 1")
+    if paths is not None and compare is None:
+        raise ValueError("synthesize: paths= (a DtwPathWriter) goes with compare= (a DtwWriter): the path is the one the "
+                         "comparison's recursion chose")
     if writer is None and scores is None and alignments is None and compare is None:
         raise ValueError("synthesize: a PackedSpecWriter is required (or a ScoreWriter as scores=, or an AlignmentWriter as "
                          "alignments=): there is nothing to write")
     scored = scores is not None
     compared = compare is not None
+    pathed = paths is not None
     if compared:
         if getattr(dataset, "teacher_forcing", False):
             raise ValueError("synthesize: compare= scores free synthesis; a teacher-forced dataset already has the "
@@ -139,19 +156,20 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                             and getattr(dataset, "style", None) is None and getattr(dataset, "styles", None) is None)
     was_training = model.training
     model.eval()
-    files, frames, alignment_files = [], 0, []
+    files, frames, alignment_files, path_files = [], 0, [], []
     aligned = alignments is not None
     if aligned:
         vp = model.config.model.variance_predictors
         levels = {"duration": "phone", "pitch": vp.pitch.level.value, "energy": vp.energy.level.value}
         teacher_forced = bool(getattr(dataset, "teacher_forcing", False))
         duration_source = ("aligner" if learn_alignment else "given") if teacher_forced else "predicted"
-    # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys, alignment block, recorded frame counts)], oldest first
+    # [(slot, copy event, header floats, total floats, expected offsets, CPU batch, positions, keys, alignment block, recorded
+    #   frame counts, path block)], oldest first
     pending = []
 
     def finish(job):
         nonlocal frames
-        slot, event, hdr, total, expect, cpu_batch, positions, keys, block, ref_frames = job
+        slot, event, hdr, total, expect, cpu_batch, positions, keys, block, ref_frames, pathblock = job
         event.synchronize()   # the one wait of this batch
         base = hdr
         if writer is not None:
@@ -189,6 +207,19 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 compare.add(pos, dict(basename=cpu_batch["basename"][k], speaker=cpu_batch["speaker"][k],
                                       language=cpu_batch["language"][k], raw_text=cpu_batch["raw_text"][k], total=totals[k],
                                       steps=cells[k], frames=(expect[k + 1] - expect[k]) // n_mels, ref_frames=ref_frames[k]))
+            if pathed:
+                pblock, pmembers = pathblock
+                tab = _Slot.table(B)
+                for name, (k, start, want, level) in pmembers.items():
+                    got = slot.host[k * tab:k * tab + 2 * len(want)].view(torch.int64).tolist()
+                    if got != want:
+                        raise RuntimeError(f"synthesize: the warping path's {name} lengths on the GPU differ from the host's "
+                                           f"({'token' if level == 'phone' else 'frame'} counts that do not match the batch's?): "
+                                           f"offsets {got} against {want}")
+                path_files.extend(zip(positions, paths.write_packed(
+                    slot.host[base:base + pblock], {name: (start, want) for name, (_, start, want, _) in pmembers.items()},
+                    cpu_batch, positions, [n // n_mels for n in _diff(expect)], ref_frames, totals, cells)))
+                base += pblock   # (the payload lies behind the path block)
         frames += expect[-1] // n_mels
         if writer is not None:
             files.extend(writer.write_packed(slot.host[base:base + total], offsets, cpu_batch, positions))
@@ -220,7 +251,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 expect = [0]
                 for n in lens_host.tolist():
                     expect.append(expect[-1] + int(n) * C)
-                hdr = _Slot.header(B, scored, len(levels) if aligned else 0, compared)
+                hdr = _Slot.header(B, scored, (len(levels) if aligned else 0) + (len(paths.MEMBERS) if pathed else 0), compared)
                 total = expect[-1] if writer is not None else 0   # (scores / comparison only: the header is all that travels)
                 slot = slots[i % depth]   # (its previous batch, i - depth, has been finished: see the drain below)
                 ablock, worst, block = 0, 0, None
@@ -241,20 +272,47 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                         ablock += want[-1]
                     ablock, worst = -(-ablock // 4) * 4, -(-worst // 4) * 4
                     block = (ablock, members)
-                base = hdr + ablock
-                slot.reserve(hdr + worst + (B * Tm * C if writer is not None else 0))
+                pblock, pworst, pathblock = 0, 0, None
+                if pathed:
+                    # the path block, laid out like the alignment block and behind it: sizes from the same host lengths,
+                    # B * T elements reserved per member.  Its tables follow the alignment block's in the header
+                    pcounts = {"phone": cpu_batch["src_lens"].tolist(), "frame": lens_host.tolist()}
+                    reserve = {"phone": out["duration_rounded"].numel(), "frame": B * max(Tm, 1)}
+                    pmembers = {}
+                    for k, name in enumerate(paths.MEMBERS):
+                        level = "phone" if name == "duration" else "frame"
+                        want = [0]
+                        for n in pcounts[level]:
+                            want.append(want[-1] + int(n))
+                        pmembers[name] = (1 + (len(levels) if aligned else 0) + k, pblock, want, level)
+                        pworst = max(pworst, pblock + reserve[level])
+                        pblock += want[-1]
+                    pblock, pworst = -(-pblock // 4) * 4, -(-pworst // 4) * 4
+                    pathblock = (pblock, pmembers)
+                base = hdr + ablock + pblock
+                slot.reserve(hdr + max(worst, ablock + pworst) + (B * Tm * C if writer is not None else 0))
                 keys = None
                 if scored:
                     _, keys = model.utterance_losses(out, cpu_batch, out=slot.dev[hdr - _COLS * B:hdr].view(B, _COLS))
                 if compared:
                     at = hdr - _Slot.dtw_table(B)
-                    model.mel_dtw(out, ref, ref_lens, out=slot.dev[at:at + 2 * B])
+                    if pathed:
+                        path_rows = dict(zip(paths.MEMBERS, (out["duration_rounded"],) + tuple(
+                            model.mel_dtw_paths(out, ref, ref_lens, out=slot.dev[at:at + 2 * B])[2:])))
+                    else:
+                        model.mel_dtw(out, ref, ref_lens, out=slot.dev[at:at + 2 * B])
                 if aligned:
                     tab = _Slot.table(B)
                     H.pack_rows([(rows[name], out["src_lens" if level == "phone" else "tgt_lens"],
                                   slot.dev[hdr + start:hdr + start + rows[name].numel()],
                                   slot.dev[(1 + k) * tab:(1 + k) * tab + 2 * (B + 1)].view(torch.int64))
                                  for k, (name, (start, _, level)) in enumerate(members.items())], B)
+                if pathed:
+                    tab, at = _Slot.table(B), hdr + ablock
+                    H.pack_rows([(path_rows[name], out["src_lens" if level == "phone" else "tgt_lens"],
+                                  slot.dev[at + start:at + start + path_rows[name].numel()],
+                                  slot.dev[k * tab:k * tab + 2 * (B + 1)].view(torch.int64))
+                                 for name, (k, start, _, level) in pmembers.items()], B)
                 if writer is not None:
                     H.pack_spec(y, out["tgt_lens"], slot.dev[base:base + B * Tm * C], slot.dev[:2 * (B + 1)].view(torch.int64))
                 packed_ev = torch.cuda.Event()
@@ -265,7 +323,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                     copied_ev = torch.cuda.Event()
                     copied_ev.record(copy_stream)
                 slot.dev.record_stream(copy_stream)
-                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys, block, ref_frames))
+                pending.append((slot, copied_ev, hdr, total, expect, cpu_batch, positions, keys, block, ref_frames, pathblock))
                 # the next batch's forward is enqueued before this batch's copy is waited for: only what exceeds
                 # depth - 1 batches in flight is finished now
                 while len(pending) > depth - 1:
@@ -284,6 +342,8 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
         res["alignment_files"] = alignment_files
         if teacher_forced and learn_alignment:
             res["duration_files"] = list(alignments.duration_files)
+    if pathed:
+        res["path_files"] = [path for _, path in sorted(path_files)]   # (one per entry, written batch by batch: input order)
     return res
 
 

@@ -737,13 +737,32 @@ int fs2hip_bn_act_bwd_lens(const float* dout, const float* y, const float* stats
  *               total and steps are written for every u; nothing outside the box is read.  One wavefront per utterance,
  *               64 columns at a time, ceil(r / 64) * (n + 63) dependent steps at most.  T1 <= FS2_DTW_MAX_T1 (8 bytes of LDS
  *               per row beside the 16 KiB cost ring).
+ *   dtw_dirs    dtw that also keeps, for every cell of the box, the predecessor it took: dirs [B][T1][T2], ONE BYTE per cell
+ *               (no packed form), 0 = diagonal (i-1, j-1), 1 = up (i-1, j), 2 = left (i, j-1); cell (0, 0) gets 0.  total
+ *               and steps are bit-equal to dtw's on the same matrix.  No byte of dirs outside the box is written; an empty
+ *               box writes total = 0, steps = 0 and no direction.  The codes leave through a second LDS ring of 64 x 64
+ *               bytes (a row of 64 codes per store), which the 64 KiB of dynamic LDS has to hold as well:
+ *               T1 <= FS2_DTW_PATH_MAX_T1 = (65536 - 16384 - 4096) / 8.
+ *   dtw_path    the backtrack: from (n-1, r-1) the walk follows dirs to (0, 0) and writes, for every row i < n of the box,
+ *                   ref_first[u][i], ref_last[u][i]   the smallest and largest column j of the path's cells in row i
+ *                   frame_cost[u][i]                  cost[i][ref_last] + cost[i][ref_last - 1] + ... + cost[i][ref_first]
+ *               (all [B][T1]; the fp32 sum starts from the cell at ref_last and adds the others in the order the walk meets
+ *               them, j descending, without contraction: bit-defined).  Rows i >= n are never written, an empty box writes
+ *               nothing, nothing outside the box is read.  In column 0 the walk only goes up and in row 0 only left
+ *               whatever dirs says, and any code but 1 and 2 counts as diagonal, so no content of dirs leads outside the
+ *               box.  One wavefront per utterance, at most n + r - 1 dependent steps, read from LDS tiles of 32 x 64 cells.
  * FS2HIP_EINVAL, before any launch: a null pointer, a non-positive extent, an extent beyond the limits above. */
 #define FS2_FRAME_DIST_MAX_C 204
 #define FS2_DTW_MAX_T1 6144
+#define FS2_DTW_PATH_MAX_T1 5632
 int fs2hip_frame_dist(const float* a, const int* a_lens, const float* b, const int* b_lens, float* cost, int B, int T1,
                       int T2, int C, void* stream);
 int fs2hip_dtw(const float* cost, const int* lens1, const int* lens2, float* total, int* steps, int B, int T1, int T2,
                void* stream);
+int fs2hip_dtw_dirs(const float* cost, const int* lens1, const int* lens2, float* total, int* steps, unsigned char* dirs,
+                    int B, int T1, int T2, void* stream);
+int fs2hip_dtw_path(const float* cost, const unsigned char* dirs, const int* lens1, const int* lens2, int* ref_first,
+                    int* ref_last, float* frame_cost, int B, int T1, int T2, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
