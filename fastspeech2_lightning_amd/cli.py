@@ -136,6 +136,18 @@ def build_parser() -> argparse.ArgumentParser:
                          "BatchNorm statistics over the valid positions, the GRU stopped after each utterance's own steps), so "
                          "the style does not follow the batch's or the bucket's padding (FastSpeech2.style_lengths).  Ignored "
                          "when model.use_global_style_token_module is false")
+    tr.add_argument("--val-synthesis", action="store_true",
+                    help="every validation also runs the model FREE on each validation batch (its own durations, pitch and energy; "
+                         "exact lengths) and scores the result against the batch's recorded mel by DTW (fs2hip_frame_dist + "
+                         "fs2hip_dtw): validation/mel_dtw, validation/frame_ratio, validation/synth_scored and "
+                         "validation/synth_empty join the losses in metrics.jsonl.  Training steps are not touched")
+    tr.add_argument("--val-cepstra", type=int, default=None, metavar="K",
+                    help="with --val-synthesis: also validation/cep_dtw, the DTW distance on the cepstral coefficients 1..K of "
+                         "both sides along its own cheapest path (fs2hip_cepstra; MCD-DTW's distance without the dB factor)")
+    tr.add_argument("--monitor", default=MONITOR, metavar="KEY",
+                    help="the validation metric that selects best.ckpt, smaller is better (default: %(default)s; also the "
+                         "other validation/*_loss terms of the model, validation/mel_dtw with --val-synthesis and "
+                         "validation/cep_dtw with --val-cepstra).  Resuming with another key starts best over")
     tr.add_argument("--dry-run", action="store_true", help="resolve config, filelists, look-up tables and the run directory, print the plan, touch no GPU "
                                                              "(with --bucket-lengths: also reads every item's lengths once and writes the cache "
                                                              "<run dir>/lengths.json, then prints the bucket table)")
@@ -182,6 +194,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "FREE synthesis and its recorded mel DIR/spec/<basename>--... (the preprocessed folder -T would read), "
                          "mean frame distance along the warping path, worst first (fs2hip_frame_dist + fs2hip_dtw; implies "
                          "--exact-lengths).  Not with -T: teacher forcing fixes the lengths, --return-scores is its measure")
+    sy.add_argument("--cepstra", type=int, default=None, metavar="K",
+                    help="with --compare-to: dtw-<step>.psv gains cep_dtw, cep_total and cep_steps, the same distance on the "
+                         "cepstral coefficients 1..K of both sides (orthonormal DCT-II of every frame, c0 dropped: fs2hip_cepstra) "
+                         "along ITS cheapest path, as MCD-DTW takes it: the plain Euclidean distance on c1..cK of the model's own "
+                         "log-mel features (natural-log mels: times 10*sqrt(2)/ln(10) for the conventional dB figure)")
     sy.add_argument("--scores-only", action="store_true",
                     help="with --return-scores or --compare-to: write the score file and no spectrograms")
     sy.add_argument("--write-paths", action="store_true",
@@ -265,6 +282,51 @@ def style_lengths_mode(args, config) -> dict:
     return {"style_lengths": asked}
 
 
+def check_cepstra(K, n_mels: int, flag: str) -> None:
+    """``--cepstra`` / ``--val-cepstra``: 1 .. min(n_mels - 1, 64) coefficients (``fs2hip_cepstra``'s limits)."""
+    from .hip import CEPSTRA_MAX_K
+    top = min(int(n_mels) - 1, CEPSTRA_MAX_K)
+    if K is not None and not 1 <= K <= top:
+        raise SystemExit(f"{flag} {K}: expected 1 .. {top} coefficients (at most n_mels - 1 = {int(n_mels) - 1} and "
+                         f"{CEPSTRA_MAX_K})")
+
+
+def monitor_keys(config, val_synthesis: bool = False, val_cepstra=None) -> list:
+    """The metrics ``--monitor`` may name: what this run's validation produces and smaller is better for."""
+    terms = ["pitch", "energy", "duration", "spec"] + (["postnet"] if config.model.use_postnet else [])
+    if config.model.learn_alignment:
+        terms += ["attn_ctc", "attn_bin"]
+    keys = [MONITOR] + [f"validation/{k}_loss" for k in terms]
+    if val_synthesis:
+        keys.append("validation/mel_dtw")
+        if val_cepstra is not None:
+            keys.append("validation/cep_dtw")
+    return keys
+
+
+def val_synthesis_mode(args, config) -> dict:
+    """``--val-synthesis``, ``--val-cepstra`` and ``--monitor`` resolved against the model, refusing what cannot work before
+    anything is loaded: what the trainer runs with and what a dry run reports (the first two only when asked for)."""
+    from .hip import DTW_MAX_T1
+    asked, K = bool(getattr(args, "val_synthesis", False)), getattr(args, "val_cepstra", None)
+    monitor = getattr(args, "monitor", None) or MONITOR
+    if K is not None and not asked:
+        raise SystemExit("--val-cepstra goes with --val-synthesis: the cepstral distance is taken on the free synthesis")
+    if asked:
+        check_cepstra(K, config.preprocessing.audio.n_mels, "--val-cepstra")
+        if config.model.max_length > DTW_MAX_T1:
+            raise SystemExit(f"--val-synthesis: model.max_length = {config.model.max_length} exceeds the DTW kernel's "
+                             f"{DTW_MAX_T1} synthesized frames (fs2hip_dtw keeps 8 bytes of LDS per row)")
+    offered = monitor_keys(config, asked, K)
+    if monitor not in offered:
+        raise SystemExit(f"--monitor {monitor}: this run does not produce it; choose from {', '.join(offered)}"
+                         + ("" if asked else " (validation/mel_dtw needs --val-synthesis, validation/cep_dtw --val-cepstra)"))
+    out = {"monitor": monitor}
+    if asked:
+        out.update(val_synthesis=True, val_cepstra=K)
+    return out
+
+
 def bucket_count(args) -> Optional[int]:
     """``--bucket-lengths [N]``: None = off, otherwise the number of buckets (no value: the launch-plan limit).  More
     buckets than plans are allowed but warned about once: the limit is not raised (a plan's pool is gigabytes)."""
@@ -331,6 +393,8 @@ class Trainer:
             self.global_step, self.epoch = self.model.restore_training_state(ckpt, self.opt)
             self.sched.last_epoch = self.opt.steps_done()  # host mirror of the device-resident schedule
             self.best = ckpt.get("fs2l_best_monitor", float("inf"))
+            if ckpt.get("fs2l_monitor", MONITOR) != getattr(args, "monitor", MONITOR):
+                self.best = float("inf")   # best under another metric says nothing about this one: start over
             self.batches_in_epoch = int(ckpt.get("fs2l_batches_in_epoch", 0))
         else:
             self.best, self.batches_in_epoch = float("inf"), 0
@@ -343,6 +407,11 @@ class Trainer:
         self._tiles_shared = world == 1
         self.n_buckets = bucket_count(args)
         cfg = self.model.config
+        mode = val_synthesis_mode(args, cfg)
+        self.monitor, self.val_synthesis = mode["monitor"], None
+        if mode.get("val_synthesis"):
+            from .data import SynthesisValidation
+            self.val_synthesis = SynthesisValidation(cepstra=mode["val_cepstra"])
         self.model.style_lengths = style_lengths_mode(args, cfg)["style_lengths"]
         prior = attn_prior_mode(args, cfg)["attn_prior"]
         self.train_set = FeatureDataset(p["train_rows"], cfg, self.model.lang2id, self.model.speaker2id, attn_prior=prior)
@@ -439,16 +508,24 @@ class Trainer:
         cfg = self.model.config
         if self.sync is not None:
             self.sync.broadcast_buffers(0)  # DDP broadcast_buffers: every rank evaluates with rank 0's running statistics
-        means = validate(self.model, self.batches(self.val_set, False, 0, cfg.training.val_data_workers))
+        if self.val_synthesis is None:
+            means = validate(self.model, self.batches(self.val_set, False, 0, cfg.training.val_data_workers))
+        else:
+            means = validate(self.model, self.batches(self.val_set, False, 0, cfg.training.val_data_workers),
+                             synthesis=self.val_synthesis)
         self.model.train()
         self.log(means)
-        return means.get(MONITOR, float("inf"))
+        if self.monitor in ("validation/mel_dtw", "validation/cep_dtw") and not means.get("validation/synth_scored"):
+            return float("inf")   # (a mean over no utterance is logged as 0.0: it must not win)
+        return means.get(self.monitor, float("inf"))
 
     def save(self, name: str):
         if self.rank != 0:
             return
         ckpt = self.model.checkpoint_dict(self.global_step, self.epoch, self.opt)
         ckpt["fs2l_best_monitor"] = self.best
+        if self.monitor != MONITOR:
+            ckpt["fs2l_monitor"] = self.monitor   # (absent: the default -- checkpoints of runs without --monitor do not change)
         ckpt["fs2l_batches_in_epoch"] = self.batches_in_epoch
         path = self.p["ckpt_dir"] / name
         tmp = path.with_suffix(".tmp")
@@ -621,6 +698,7 @@ def gather_from_ranks(procs: list, queue, n: int, timeout: float = 300.0, poll_s
 
 def train(args, argv) -> int:
     p = plan(args)
+    mode = val_synthesis_mode(args, p["config"])
     if args.dry_run:
         n_buckets = bucket_count(args)
         print(json.dumps({
@@ -628,7 +706,7 @@ def train(args, argv) -> int:
             "config": str(args.config_file), "run_dir": str(p["run_dir"]), "resume": str(p["resume"]) if p["resume"] else None,
             "train_utterances": len(p["train_rows"]), "validation_utterances": len(p["val_rows"]),
             "lang2id": p["lang2id"], "speaker2id": p["speaker2id"], "batch_size": p["config"].training.batch_size,
-            "max_steps": p["max_steps"], "max_epochs": p["max_epochs"], "monitor": MONITOR,
+            "max_steps": p["max_steps"], "max_epochs": p["max_epochs"], **mode,
             "gradient_clip_val": GRADIENT_CLIP_VAL, "learn_alignment": p["config"].model.learn_alignment,
             **attn_prior_mode(args, p["config"]), **style_lengths_mode(args, p["config"]),
             "stats": sorted(p["stats"])}))
@@ -663,7 +741,7 @@ def train(args, argv) -> int:
         import torch.distributed as dist
         dist.destroy_process_group()
     if rank == 0:
-        print(json.dumps({"finished": True, "global_step": steps, "epoch": trainer.epoch, "best_" + MONITOR: trainer.best,
+        print(json.dumps({"finished": True, "global_step": steps, "epoch": trainer.epoch, "best_" + trainer.monitor: trainer.best,
                           "checkpoint": str(p["ckpt_dir"] / "last.ckpt")}), flush=True)
     return 0
 
@@ -833,6 +911,9 @@ def synthesize_command(args) -> int:
     if args.compare_to is not None and args.texts:
         raise SystemExit("--compare-to needs --filelist (-f): the recorded mel of a row is found by its basename, and a --text "
                          "(-t) has none")
+    if args.cepstra is not None and args.compare_to is None:
+        raise SystemExit("--cepstra goes with --compare-to: the cepstral distance is taken between a free synthesis and its "
+                         "recording")
     if args.write_paths and args.compare_to is None:
         raise SystemExit("--write-paths goes with --compare-to: the path is the one that leads to the recording")
     if args.scores_only and not (args.return_scores or args.compare_to is not None):
@@ -859,7 +940,11 @@ def synthesize_command(args) -> int:
                                attn_prior=attn_prior_mode(args, config)["attn_prior"], compare_dir=args.compare_to)
     sort = not args.no_sort
     scores = ScoreWriter(args.output_dir, global_step) if args.return_scores else None
-    compare = DtwWriter(args.output_dir, global_step) if args.compare_to is not None else None
+    check_cepstra(args.cepstra, config.preprocessing.audio.n_mels, "--cepstra")
+    compare = None
+    if args.compare_to is not None:
+        compare = (DtwWriter(args.output_dir, global_step) if args.cepstra is None
+                   else DtwWriter(args.output_dir, global_step, cepstra=args.cepstra))
     if args.dry_run:
         plan = {
             "checkpoint": str(args.model_path), "global_step": global_step, "output_dir": str(args.output_dir),
@@ -881,6 +966,8 @@ def synthesize_command(args) -> int:
         if compare is not None:
             plan["compare_to"] = str(args.compare_to)
             plan["dtw_file"] = str(compare.path)
+            if args.cepstra is not None:
+                plan["cepstra"] = args.cepstra
             if args.write_paths:
                 paths = DtwPathWriter(args.output_dir, global_step, dataset.text_processor.symbols)
                 plan["dtw_tokens_file"] = str(paths.path)

@@ -696,13 +696,24 @@ class DtwWriter:
     mean distance per aligned frame pair, ``frames`` / ``ref_frames`` the synthesized and recorded lengths and
     ``frame_ratio`` their quotient.  ``mel_dtw`` and ``frame_ratio`` are empty fields when ``steps`` or ``ref_frames`` is 0.
     Rows are sorted by ``-mel_dtw``, rows without one last, ties in input order.  ``add`` collects a record in any order
-    (``position``: the entry's place in the input); ``close`` sorts, writes and returns the path."""
+    (``position``: the entry's place in the input); ``close`` sorts, writes and returns the path.
+
+    ``cepstra=K`` (``fs2l synthesize --compare-to DIR --cepstra K``): the file gains the columns ``cep_dtw``, ``cep_total`` and
+    ``cep_steps`` behind ``steps`` -- ``FastSpeech2.mel_dtw(..., cepstra=K)``'s distance on the cepstral coefficients 1 .. K
+    along ITS cheapest path, ``cep_dtw = cep_total / cep_steps`` (empty without steps): the plain Euclidean distance on
+    c1 .. cK of the model's own log-mel features (for natural-log mels, ``10 * sqrt(2) / ln(10)`` times it is the
+    conventional figure in dB).  Records must then carry ``cep_total`` and ``cep_steps``.  The sort key stays ``mel_dtw``;
+    without ``cepstra`` the file is what it always was (``fields`` is ``FIELDS``)."""
 
     FIELDS = ("basename", "speaker", "language", "mel_dtw", "total", "steps", "frames", "ref_frames", "frame_ratio", "raw_text")
+    CEPSTRA_FIELDS = ("cep_dtw", "cep_total", "cep_steps")
 
-    def __init__(self, output_dir, global_step: int = 0):
+    def __init__(self, output_dir, global_step: int = 0, cepstra=None):
         self.dir, self.global_step = Path(output_dir), int(global_step)
         self.records = {}
+        self.cepstra = None if cepstra is None else int(cepstra)
+        at = self.FIELDS.index("steps") + 1
+        self.fields = self.FIELDS if self.cepstra is None else self.FIELDS[:at] + self.CEPSTRA_FIELDS + self.FIELDS[at:]
 
     @property
     def path(self) -> Path:
@@ -714,10 +725,14 @@ class DtwWriter:
         position = int(position)
         if position in self.records:
             raise ValueError(f"DtwWriter: position {position} delivered twice")
-        missing = [k for k in ("basename", "total", "steps", "frames", "ref_frames") if k not in record]
+        need = ("basename", "total", "steps", "frames", "ref_frames") + (("cep_total", "cep_steps") if self.cepstra else ())
+        missing = [k for k in need if k not in record]
         if missing:
             raise ValueError(f"DtwWriter: the record of position {position} lacks {missing}")
         rec = dict(record)
+        if self.cepstra is not None:
+            rec["cep_total"], rec["cep_steps"] = float(rec["cep_total"]), int(rec["cep_steps"])
+            rec["cep_dtw"] = rec["cep_total"] / rec["cep_steps"] if rec["cep_steps"] > 0 else None
         for k in ("steps", "frames", "ref_frames"):
             rec[k] = int(rec[k])
         rec["total"] = float(rec["total"])
@@ -734,7 +749,7 @@ class DtwWriter:
         import csv
         self.dir.mkdir(parents=True, exist_ok=True)
         with open(self.path, "w", encoding="utf8", newline="") as f:
-            w = csv.DictWriter(f, fieldnames=list(self.FIELDS), delimiter="|", restval="", extrasaction="ignore",
+            w = csv.DictWriter(f, fieldnames=list(self.fields), delimiter="|", restval="", extrasaction="ignore",
                                lineterminator="\n")
             w.writeheader()
             for r in self.sorted_records():
@@ -1246,20 +1261,108 @@ def truncate_basename(basename: str, max_length: int = 20) -> str:
     return cleaned[:max_length] + "-" + hashlib.sha1(bytes(basename, encoding="UTF-8")).hexdigest()[:8]
 
 
-def validate(model, batches: Iterable[dict], process_group=None) -> dict:
+class SynthesisValidation:
+    """Options of ``validate(..., synthesis=...)`` (``fs2l train --val-synthesis [--val-cepstra K]``): ``cepstra`` = K adds the
+    cepstral distance (``FastSpeech2.mel_dtw(..., cepstra=K)``), None leaves the mel distance alone."""
+
+    def __init__(self, cepstra=None):
+        self.cepstra = None if cepstra is None else int(cepstra)
+        self.sums = None   # the six SYNTHESIS_SUMS of the last pass (after the ranks' exchange), for whoever wants the counts
+
+
+#: what a free forward must not see: their absence is what turns teacher forcing off
+_TARGET_KEYS = ("mel_lens", "mel", "duration", "pitch", "energy")
+#: the sums ``synthesis_metrics`` returns, in order (all-reduced across ranks as ``validate`` reduces its loss sums)
+SYNTHESIS_SUMS = ("mel_dtw_sum", "cep_dtw_sum", "scored", "empty", "frames", "ref_frames")
+
+
+def free_batch(model, batch: dict) -> dict:
+    """The validation ``batch`` as free inference takes it: without the targets, ``max_mel_len`` = the cap
+    ``config.model.max_length``, and -- a GST model -- every utterance's own recording at its own length as its style
+    (what ``fs2l synthesize -T --exact-lengths`` feeds)."""
+    free = {k: v for k, v in batch.items() if k not in _TARGET_KEYS}
+    free.update({k: None for k in _TARGET_KEYS})   # (a collated inference batch carries the keys as None)
+    free["max_mel_len"] = int(model.config.model.max_length)
+    if getattr(model, "gst", None) is not None:
+        free["mel_style_reference"] = batch["mel"]
+        free["style_reference_lens"] = batch["mel_lens"]
+    return free
+
+
+def synthesis_metrics_from_sums(sums, cepstra: bool) -> dict:
+    """The validation metrics of free synthesis from the six ``SYNTHESIS_SUMS`` (float64 on the host).  A mean over no
+    utterance and a ratio to no frame are reported as 0.0: ``validation/synth_scored`` says how many the mean stands for."""
+    mel, cep, scored, empty, frames, ref_frames = (float(v) for v in sums)
+    out = {"validation/mel_dtw": mel / scored if scored > 0 else 0.0}
+    if cepstra:
+        out["validation/cep_dtw"] = cep / scored if scored > 0 else 0.0
+    out["validation/frame_ratio"] = frames / ref_frames if ref_frames > 0 else 0.0
+    out["validation/synth_scored"] = int(scored)
+    out["validation/synth_empty"] = int(empty)
+    return out
+
+
+def synthesis_metrics(total, steps, frames, ref_frames, cep_total=None, cep_steps=None) -> tuple:
+    """``(metrics, sums)`` of free synthesis over the validation utterances, from ``FastSpeech2.mel_dtw``'s per-utterance
+    results and the frame counts (sequences or arrays, one entry per utterance; float64 arithmetic on the host):
+
+        validation/mel_dtw       mean over the utterances with ``steps > 0`` of ``total / steps``
+        validation/cep_dtw       the same mean of ``cep_total / cep_steps`` (only when those are given)
+        validation/frame_ratio   sum of synthesized frames / sum of recorded frames
+        validation/synth_scored  utterances with ``steps > 0``
+        validation/synth_empty   the others: a model that predicts no frame for an utterance gives (0, 0), which is
+                                 counted, not averaged
+
+    ``sums``: the six ``SYNTHESIS_SUMS`` the metrics are quotients of -- what ranks add up before
+    ``synthesis_metrics_from_sums`` divides."""
+    total = np.asarray(total, dtype=np.float64).reshape(-1)
+    steps = np.asarray(steps, dtype=np.int64).reshape(-1)
+    frames = np.asarray(frames, dtype=np.int64).reshape(-1)
+    ref_frames = np.asarray(ref_frames, dtype=np.int64).reshape(-1)
+    if not (len(total) == len(steps) == len(frames) == len(ref_frames)):
+        raise ValueError("synthesis_metrics: total, steps, frames and ref_frames differ in length")
+    scored = steps > 0
+    mel = float(np.sum(total[scored] / steps[scored])) if scored.any() else 0.0
+    cep = 0.0
+    if cep_total is not None:
+        cep_total = np.asarray(cep_total, dtype=np.float64).reshape(-1)
+        cep_steps = np.asarray(cep_steps, dtype=np.int64).reshape(-1)
+        if len(cep_total) != len(total) or len(cep_steps) != len(total):
+            raise ValueError("synthesis_metrics: cep_total / cep_steps differ in length from total")
+        if not np.array_equal(cep_steps > 0, scored):
+            raise ValueError("synthesis_metrics: the cepstral and the mel distance disagree on which utterances have a path")
+        cep = float(np.sum(cep_total[scored] / cep_steps[scored])) if scored.any() else 0.0
+    sums = [mel, cep, float(scored.sum()), float(len(steps) - scored.sum()), float(frames.sum()), float(ref_frames.sum())]
+    return synthesis_metrics_from_sums(sums, cep_total is not None), sums
+
+
+def validate(model, batches: Iterable[dict], process_group=None, synthesis=None) -> dict:
     """Mean of every loss term over the validation batches and over the ranks (what
-    ``log_dict(..., sync_dist=True)`` reports and checkpoint selection monitors as ``validation/total_loss``)."""
+    ``log_dict(..., sync_dist=True)`` reports and checkpoint selection monitors as ``validation/total_loss``).
+
+    ``synthesis`` (a ``SynthesisValidation``; None: exactly the above): every batch is used twice in the one pass -- after
+    the teacher-forced ``validation_step``, ``forward(free_batch(model, batch), inference=True, exact_lengths=True)`` in
+    eval mode runs the model on its own durations, pitch and energy, and ``FastSpeech2.mel_dtw`` scores the result against
+    the batch's recorded mel.  The per-utterance results stay in GPU memory and are read back once, after the last batch
+    (the free forward's own read of the frame totals is the only other synchronisation); ``synthesis_metrics`` turns them
+    into ``validation/mel_dtw``, ``validation/cep_dtw`` (with ``cepstra``), ``validation/frame_ratio``,
+    ``validation/synth_scored`` and ``validation/synth_empty``, in the same dict as the losses.  No training state is
+    touched: eval mode, no plan, no BatchNorm buffer, no dropout counter."""
     import torch.distributed as dist
 
     total, n = None, 0
     keys = None
+    kept = []   # per batch: the int32 rows [total bits, steps, frames, ref_frames (, cep_total bits, cep_steps)] on the device
     for batch in batches:
         losses = model.validation_step(batch)
         keys = keys or list(losses)
         vec = torch.stack([losses[k].detach().float() for k in keys])
         total = vec if total is None else total + vec
         n += 1
+        if synthesis is not None:
+            kept.append(_free_synthesis_rows(model, batch, synthesis.cepstra))
     distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1
+    synth = _synthesis_summary(model, kept, synthesis, distributed, process_group) if synthesis is not None else {}
     if total is None and not distributed:
         return {}
     if distributed:
@@ -1276,4 +1379,41 @@ def validate(model, batches: Iterable[dict], process_group=None) -> dict:
     if distributed:
         dist.all_reduce(stat, group=process_group)
     mean = (stat[:-1] / stat[-1]).cpu()
-    return {f"validation/{k}_loss": float(v) for k, v in zip(keys, mean)}
+    return {**{f"validation/{k}_loss": float(v) for k, v in zip(keys, mean)}, **synth}
+
+
+def _free_synthesis_rows(model, batch: dict, cepstra) -> torch.Tensor:
+    """One validation batch through free inference and ``mel_dtw``: ``[4 or 6, B]`` int32 in GPU memory (fp32 rows as bit
+    patterns), nothing read back beyond the forward's own frame totals."""
+    was = model.training
+    model.eval()
+    try:
+        out = model(free_batch(model, batch), inference=True, exact_lengths=True)
+        res = model.mel_dtw(out, batch["mel"], batch["mel_lens"], cepstra=cepstra)
+        Tm = out[model.output_key].shape[1]
+        rows = [res[0].view(torch.int32), res[1], out["tgt_lens"].clamp(0, Tm).to(torch.int32),
+                batch["mel_lens"].to(torch.int32)]
+        if cepstra is not None:
+            rows += [res[2].view(torch.int32), res[3]]
+        return torch.stack(rows)
+    finally:
+        model.train(was)
+
+
+def _synthesis_summary(model, kept: list, synthesis, distributed: bool, process_group) -> dict:
+    import torch.distributed as dist
+    cep = synthesis.cepstra is not None
+    sums = [0.0] * len(SYNTHESIS_SUMS)
+    if kept:
+        host = torch.cat(kept, dim=1).cpu()   # the one read of the pass
+        f32 = lambda row: host[row].view(torch.float32).double().numpy()   # noqa: E731
+        _, sums = synthesis_metrics(f32(0), host[1].numpy(), host[2].numpy(), host[3].numpy(),
+                                    f32(4) if cep else None, host[5].numpy() if cep else None)
+    if distributed:
+        box = torch.tensor(sums, device=model.device_, dtype=torch.float64)
+        dist.all_reduce(box, group=process_group)
+        sums = box.cpu().tolist()
+    elif not kept:
+        return {}
+    synthesis.sums = list(sums)
+    return synthesis_metrics_from_sums(sums, cep)

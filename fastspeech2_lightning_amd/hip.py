@@ -165,6 +165,7 @@ SIGNATURES = {
     "fs2hip_dtw": "pppppiiip",
     "fs2hip_dtw_dirs": "ppppppiiip",
     "fs2hip_dtw_path": "pppppppiiip",
+    "fs2hip_cepstra": "ppppiiiip",
     "fs2hip_plan_op_count": "",
     "fs2hip_plan_op_id": None,      # (const char*)
     "fs2hip_plan_events_create": None,   # (void**, int)
@@ -2366,6 +2367,55 @@ def dtw_path(cost, dirs, lens1, lens2, ref_first=None, ref_last=None, frame_cost
     _ok(lib().fs2hip_dtw_path(_p(cost), _p(dirs), _p(lens1), _p(lens2), _p(ref_first), _p(ref_last), _p(frame_cost), B, T1,
                               T2, _stream()), "dtw_path")
     return ref_first, ref_last, frame_cost
+
+
+CEPSTRA_MAX_K = 64  # FS2_CEPSTRA_MAX_K
+_DCT_TABLES = {}    # (C, K, device index) -> [K, C] fp32 in GPU memory, kept for the process (launch plans may point to it)
+
+
+def dct_table_host(channels: int, K: int) -> torch.Tensor:
+    """[K, C] fp32 on the host: rows 1 .. K of the orthonormal DCT-II of length C (c0, the energy term, dropped),
+    ``table[k, m] = sqrt(2 / C) * cos(pi * (k + 1) * (m + 0.5) / C)``, every element in float64 (the host's libm, one
+    element at a time: the same bits wherever it is built) and rounded to fp32 once."""
+    import math
+    n = int(channels)
+    _req(1 <= n <= FRAME_DIST_MAX_C, f"dct_table: C = {n}: 1 .. {FRAME_DIST_MAX_C} channels")
+    _req(1 <= K <= min(n - 1, CEPSTRA_MAX_K),
+         f"dct_table: K = {K}: 1 .. min(C - 1, {CEPSTRA_MAX_K}) = {min(n - 1, CEPSTRA_MAX_K)} coefficients for C = {n}")
+    scale = math.sqrt(2.0 / n)
+    rows = [[scale * math.cos(math.pi * (k + 1) * (m + 0.5) / n) for m in range(n)] for k in range(K)]
+    return torch.tensor(rows, dtype=torch.float64).to(torch.float32)
+
+
+def dct_table(channels: int, K: int) -> torch.Tensor:
+    """``dct_table_host(C, K)`` in the current device's memory: built once per (C, K, device) and kept alive."""
+    key = (int(channels), int(K), _current_device())
+    t = _DCT_TABLES.get(key)
+    if t is None:
+        t = _DCT_TABLES[key] = dct_table_host(key[0], key[1]).to(torch.device("cuda", key[2]))
+    return t if _REC is None else plan_keep(t)
+
+
+def cepstra(x, lens, K, out=None):
+    """out [B, T, K] fp32: ``out[b, t, k] = sum_m x[b, t, m] * dct_table(C, K)[k, m]`` for ``t < lens[b]`` -- the cepstral
+    coefficients 1 .. K of every valid frame of ``x`` [B, T, C] (``fs2hip_cepstra``; the fp32 sum runs in ascending ``m``
+    without contraction, so it is bit-defined).  Lengths int32 in GPU memory, clamped to the geometry on the device; rows
+    of ``x`` beyond them are never read and rows of ``out`` beyond them are left as they are."""
+    _chk(x, name="cepstra: x"); _chk(lens, torch.int32, "cepstra: lens")
+    _req(x.dim() == 3 and x.numel() > 0, f"cepstra: x {tuple(x.shape)} is not a non-empty [B, T, C]")
+    B, T, Cc = x.shape
+    K = int(K)
+    _req(Cc <= FRAME_DIST_MAX_C, f"cepstra: C = {Cc}: at most {FRAME_DIST_MAX_C} channels (the tile's LDS)")
+    _req(1 <= K <= min(Cc - 1, CEPSTRA_MAX_K),
+         f"cepstra: K = {K}: 1 .. min(C - 1, {CEPSTRA_MAX_K}) = {min(Cc - 1, CEPSTRA_MAX_K)} coefficients for C = {Cc}")
+    _req(lens.numel() == B, f"cepstra: {lens.numel()} lengths for {B} utterances")
+    if out is None:
+        out = torch.empty(B, T, K, device=x.device, dtype=torch.float32)
+    else:
+        _chk(out, name="cepstra: out")
+        _req(tuple(out.shape) == (B, T, K), f"cepstra: out is {tuple(out.shape)}, expected {(B, T, K)}")
+    _ok(lib().fs2hip_cepstra(_p(x), _p(lens), _p(dct_table(Cc, K)), _p(out), B, T, Cc, K, _stream()), "cepstra")
+    return out
 
 
 def duration_cumsum(dur, Tm, expect=None, bad_count=None):

@@ -35,6 +35,23 @@ except Exception:  # pragma: no cover - depends on the environment
     _Base = torch.nn.Module
 
 LOSS_KEYS = ("pitch", "energy", "duration", "spec", "postnet", "attn_ctc", "attn_bin")
+
+
+def _cepstra_option(paths: bool):
+    """Adds the keyword-only option ``cepstra=K`` to ``FastSpeech2.mel_dtw`` / ``mel_dtw_paths``.  The plain methods keep the
+    parameter list they were published with -- ``(output, ref, ref_lens, out=None)``, which ``inspect.signature`` still
+    reports (it follows ``__wrapped__``) and tests/test_dtw_cpu.py pins -- and a call without the option IS the plain
+    method; with it the same worker runs the cepstral distance behind the mel one."""
+    import functools
+
+    def wrap(plain):
+        @functools.wraps(plain)
+        def method(self, output, ref, ref_lens, out=None, *, cepstra=None):
+            if cepstra is None:
+                return plain(self, output, ref, ref_lens, out)
+            return self._mel_dtw(output, ref, ref_lens, out, paths, cepstra)
+        return method
+    return wrap
 #: "32-true": keep fp32 W^T mirrors of the weights whose data gradient reduces over the model width (one transpose launch
 #: per step), so that those GEMMs run in the forward orientation on the streaming kernel.  FS2_FP32_TRANSPOSED=0: off.
 import os as _os
@@ -1397,6 +1414,7 @@ class FastSpeech2(_Base):
             table = H.utterance_losses(terms, B, bin_term=bin_term, ctc_term=ctc_term, out=out)
         return table, tuple(keys)
 
+    @_cepstra_option(paths=False)
     def mel_dtw(self, output, ref, ref_lens, out=None):
         """Dynamic-time-warping distance between an inference forward's spectrograms and recorded ones of other lengths:
         ``(total, steps)``, ``[B]`` fp32 and ``[B]`` int32 in GPU memory.  For utterance b the frames are the first
@@ -1408,9 +1426,18 @@ class FastSpeech2(_Base):
         without frames on either side gives (0, 0).  fp32 arithmetic on whatever the forward produced; two launches,
         nothing is read back.  ``out``: a ``2 * B`` fp32 device vector to fill instead of fresh tensors -- the totals, then
         the step counts as int32 bit patterns (``synthesize`` hands in a piece of the buffer that leaves the GPU with the
-        spectrograms).  The cost matrices live in a persistent buffer that only grows."""
+        spectrograms).  The cost matrices live in a persistent buffer that only grows.
+
+        ``cepstra=K``: ``(total, steps, cep_total, cep_steps)`` -- the first two bit-equal to the call without it, the last two
+        the same distance on the cepstral coefficients 1 .. K of both sides (``hip.cepstra``: orthonormal DCT-II of every
+        valid frame, c0 dropped; then ``hip.frame_dist`` with ``C = K`` and ``hip.dtw`` on the same cost buffer).  The
+        cepstral distance takes its OWN cheapest path, as MCD-DTW does, so ``cep_steps`` may differ from ``steps``.  It is
+        the plain Euclidean distance on c1 .. cK of the model's own log-mel features; for natural-log mels the
+        conventional figure in dB is ``10 * sqrt(2) / ln(10)`` times ``cep_total / cep_steps``.  ``out`` is then ``4 * B``
+        fp32: totals, steps, cepstral totals, cepstral steps.  Four more launches, nothing is read back."""
         return self._mel_dtw(output, ref, ref_lens, out, False)
 
+    @_cepstra_option(paths=True)
     def mel_dtw_paths(self, output, ref, ref_lens, out=None):
         """``mel_dtw`` with the warping path itself: ``(total, steps, ref_first, ref_last, frame_cost)``.  ``total``,
         ``steps`` and ``out`` are ``mel_dtw``'s, bit for bit; the last three are ``[B, Tm]`` (int32, int32, fp32) -- for
@@ -1418,10 +1445,11 @@ class FastSpeech2(_Base):
         those pairs' distances (``hip.dtw_dirs`` + ``hip.dtw_path``; include/fs2hip.h has the codes and the summation
         order).  Rows beyond an utterance's frames, and all rows of an utterance without frames on either side, are not
         written.  The directions, a byte per cell, live in a second grow-only persistent buffer beside the cost
-        matrices; ``Tm`` is at most ``hip.DTW_PATH_MAX_T1``.  Three launches, nothing is read back."""
+        matrices; ``Tm`` is at most ``hip.DTW_PATH_MAX_T1``.  Three launches, nothing is read back.  ``cepstra=K`` appends
+        ``mel_dtw``'s ``(cep_total, cep_steps)`` to the result (``out`` is ``4 * B`` then); the path stays the mel path."""
         return self._mel_dtw(output, ref, ref_lens, out, True)
 
-    def _mel_dtw(self, output, ref, ref_lens, out, paths):
+    def _mel_dtw(self, output, ref, ref_lens, out, paths, cepstra=None):
         if self.training:
             raise ValueError("mel_dtw needs a model in eval mode (model.eval()): the distance is an inference result")
         y, lens = output.get(self.output_key), output.get("tgt_lens")
@@ -1437,28 +1465,56 @@ class FastSpeech2(_Base):
                 raise ValueError(f"mel_dtw: ref must be [B = {B}, Tr, n_mels = {y.shape[2]}], got "
                                  f"{list(ref.shape) if torch.is_tensor(ref) else type(ref).__name__}")
             Tr = ref.shape[1]
-            total = steps = None
+            total = steps = cep_total = cep_steps = None
+            K = None
+            if cepstra is not None:
+                K, n_mels = int(cepstra), y.shape[2]
+                if not 1 <= K <= min(n_mels - 1, H.CEPSTRA_MAX_K):
+                    raise ValueError(f"mel_dtw: cepstra = {cepstra}: 1 .. min(n_mels - 1, {H.CEPSTRA_MAX_K}) = "
+                                     f"{min(n_mels - 1, H.CEPSTRA_MAX_K)} coefficients for n_mels = {n_mels}")
             if out is not None:
-                if out.dtype != torch.float32 or out.numel() != 2 * B:
-                    raise ValueError(f"mel_dtw: out must be {2 * B} fp32 values (B totals, B step counts)")
+                if K is None:
+                    if out.dtype != torch.float32 or out.numel() != 2 * B:
+                        raise ValueError(f"mel_dtw: out must be {2 * B} fp32 values (B totals, B step counts)")
+                elif out.dtype != torch.float32 or out.numel() != 4 * B:
+                    raise ValueError(f"mel_dtw: with cepstra, out must be {4 * B} fp32 values (B totals, B step counts, B "
+                                     "cepstral totals, B cepstral step counts)")
                 out = out.view(-1)
-                total, steps = out[:B], out[B:].view(torch.int32)
+                total, steps = out[:B], out[B:2 * B].view(torch.int32)
+                if K is not None:
+                    cep_total, cep_steps = out[2 * B:3 * B], out[3 * B:].view(torch.int32)
             if Tr == 0 or Tm == 0:   # nothing recorded (or synthesized) in the whole batch
                 total = H.zeros(B, device=y.device) if total is None else total.zero_()
                 steps = H.zeros(B, device=y.device, dtype=torch.int32) if steps is None else steps.zero_()
+                cep = ()
+                if K is not None:
+                    cep = (H.zeros(B, device=y.device) if cep_total is None else cep_total.zero_(),
+                           H.zeros(B, device=y.device, dtype=torch.int32) if cep_steps is None else cep_steps.zero_())
                 if paths:
                     rows = max(Tm, 1)   # (no box has a cell: nothing of these is ever defined)
                     return (total, steps, torch.empty(B, rows, device=y.device, dtype=torch.int32),
                             torch.empty(B, rows, device=y.device, dtype=torch.int32),
-                            torch.empty(B, rows, device=y.device, dtype=torch.float32))
-                return total, steps
+                            torch.empty(B, rows, device=y.device, dtype=torch.float32)) + cep
+                return (total, steps) + cep
             cost = H.persistent_buffer("mel_dtw_cost", torch.float32, B * Tm * Tr)[:B * Tm * Tr].view(B, Tm, Tr)
-            H.frame_dist(y.contiguous(), lens, ref, ref_lens, out=cost)
+            y = y.contiguous()
+            H.frame_dist(y, lens, ref, ref_lens, out=cost)
             if not paths:
-                return H.dtw(cost, lens, ref_lens, total=total, steps=steps)
-            dirs = H.persistent_buffer("mel_dtw_dirs", torch.uint8, B * Tm * Tr)[:B * Tm * Tr].view(B, Tm, Tr)
-            total, steps = H.dtw_dirs(cost, lens, ref_lens, dirs, total=total, steps=steps)
-            return (total, steps) + H.dtw_path(cost, dirs, lens, ref_lens)
+                res = H.dtw(cost, lens, ref_lens, total=total, steps=steps)
+            else:
+                dirs = H.persistent_buffer("mel_dtw_dirs", torch.uint8, B * Tm * Tr)[:B * Tm * Tr].view(B, Tm, Tr)
+                total, steps = H.dtw_dirs(cost, lens, ref_lens, dirs, total=total, steps=steps)
+                res = (total, steps) + H.dtw_path(cost, dirs, lens, ref_lens)
+            if K is None:
+                return res
+            # the cepstral distance: both sides' coefficients 1 .. K, then the same two kernels on the same cost buffer
+            # (launches of one stream are ordered: the mel recursion and its backtrack are done with it)
+            ca = H.persistent_buffer("mel_dtw_cep_out", torch.float32, B * Tm * K)[:B * Tm * K].view(B, Tm, K)
+            cb = H.persistent_buffer("mel_dtw_cep_ref", torch.float32, B * Tr * K)[:B * Tr * K].view(B, Tr, K)
+            H.cepstra(y, lens, K, out=ca)
+            H.cepstra(ref.contiguous(), ref_lens, K, out=cb)
+            H.frame_dist(ca, lens, cb, ref_lens, out=cost)
+            return tuple(res) + tuple(H.dtw(cost, lens, ref_lens, total=cep_total, steps=cep_steps))
 
     def configure_optimizers(self):
         """fs2/model.py:530-549: ``([AdamW], [{"scheduler": NoamLR, "interval": "step"}])`` -- here a

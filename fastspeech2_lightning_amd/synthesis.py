@@ -46,7 +46,9 @@ with one non-blocking copy, and ``FastSpeech2.mel_dtw`` writes every utterance's
 recording -- ``B`` totals and ``B`` step counts -- where the score table would be, at the end of the slot header (the two
 never occur together: scores need teacher forcing, which fixes the lengths and makes warping pointless).  So the batch
 still leaves in the one copy and is waited for once.  ``exact_lengths`` is forced on, as for scores.  The unit is the
-dataset entry, i.e. the filelist row.  Without ``compare`` not one launch, allocation or header byte changes.
+dataset entry, i.e. the filelist row.  A ``DtwWriter(..., cepstra=K)`` (``--cepstra K``) also asks for the distance on the
+cepstral coefficients 1 .. K (``mel_dtw(..., cepstra=K)``): the table grows to ``4 * B`` values, the cepstral totals and step
+counts behind the others, and nothing else of the slot moves.  Without ``compare`` not one launch, allocation or header byte changes.
 
 ``paths`` (a ``data.DtwPathWriter``, only with ``compare``; ``fs2l synthesize --compare-to DIR --write-paths``) adds WHERE an
 utterance is far from its recording: ``FastSpeech2.mel_dtw_paths`` also walks the warping path back, and ONE
@@ -86,13 +88,15 @@ class _Slot:
         return -(-2 * (B + 1) // 4) * 4
 
     @staticmethod
-    def header(B: int, scored: bool = False, members: int = 0, compared: bool = False) -> int:
-        return (1 + members) * _Slot.table(B) + (_COLS * B if scored else 0) + (_Slot.dtw_table(B) if compared else 0)
+    def header(B: int, scored: bool = False, members: int = 0, compared: bool = False, cepstra: bool = False) -> int:
+        return ((1 + members) * _Slot.table(B) + (_COLS * B if scored else 0)
+                + (_Slot.dtw_table(B, cepstra) if compared else 0))
 
     @staticmethod
-    def dtw_table(B: int) -> int:
-        """B totals then B step counts (int32 bit patterns), rounded up to 4 floats like every part of the header."""
-        return -(-2 * B // 4) * 4
+    def dtw_table(B: int, cepstra: bool = False) -> int:
+        """B totals then B step counts (int32 bit patterns) -- with a cepstral distance, B more of each behind them --
+        rounded up to 4 floats like every part of the header."""
+        return -(-(4 if cepstra else 2) * B // 4) * 4
 
     def reserve(self, floats: int):
         if self.dev is None or self.dev.numel() < floats:
@@ -131,6 +135,7 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
     scored = scores is not None
     compared = compare is not None
     pathed = paths is not None
+    cep = getattr(compare, "cepstra", None) if compared else None   # (DtwWriter(..., cepstra=K): the cepstral distance too)
     if compared:
         if getattr(dataset, "teacher_forcing", False):
             raise ValueError("synthesize: compare= scores free synthesis; a teacher-forced dataset already has the "
@@ -200,13 +205,19 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 scores.add(pos, rec)
         if compared:
             B = len(positions)
-            at = hdr - _Slot.dtw_table(B)
+            at = hdr - _Slot.dtw_table(B, cep is not None)
             totals = slot.host[at:at + B].tolist()
             cells = slot.host[at + B:at + 2 * B].view(torch.int32).tolist()
+            if cep is not None:
+                cep_totals = slot.host[at + 2 * B:at + 3 * B].tolist()
+                cep_cells = slot.host[at + 3 * B:at + 4 * B].view(torch.int32).tolist()
             for k, pos in enumerate(positions):
-                compare.add(pos, dict(basename=cpu_batch["basename"][k], speaker=cpu_batch["speaker"][k],
-                                      language=cpu_batch["language"][k], raw_text=cpu_batch["raw_text"][k], total=totals[k],
-                                      steps=cells[k], frames=(expect[k + 1] - expect[k]) // n_mels, ref_frames=ref_frames[k]))
+                rec = dict(basename=cpu_batch["basename"][k], speaker=cpu_batch["speaker"][k],
+                           language=cpu_batch["language"][k], raw_text=cpu_batch["raw_text"][k], total=totals[k],
+                           steps=cells[k], frames=(expect[k + 1] - expect[k]) // n_mels, ref_frames=ref_frames[k])
+                if cep is not None:
+                    rec.update(cep_total=cep_totals[k], cep_steps=cep_cells[k])
+                compare.add(pos, rec)
             if pathed:
                 pblock, pmembers = pathblock
                 tab = _Slot.table(B)
@@ -251,7 +262,8 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 expect = [0]
                 for n in lens_host.tolist():
                     expect.append(expect[-1] + int(n) * C)
-                hdr = _Slot.header(B, scored, (len(levels) if aligned else 0) + (len(paths.MEMBERS) if pathed else 0), compared)
+                hdr = _Slot.header(B, scored, (len(levels) if aligned else 0) + (len(paths.MEMBERS) if pathed else 0), compared,
+                                   cep is not None)
                 total = expect[-1] if writer is not None else 0   # (scores / comparison only: the header is all that travels)
                 slot = slots[i % depth]   # (its previous batch, i - depth, has been finished: see the drain below)
                 ablock, worst, block = 0, 0, None
@@ -295,12 +307,13 @@ def synthesize(model, dataset, batch_size: int, control=None, writer=None, sort:
                 if scored:
                     _, keys = model.utterance_losses(out, cpu_batch, out=slot.dev[hdr - _COLS * B:hdr].view(B, _COLS))
                 if compared:
-                    at = hdr - _Slot.dtw_table(B)
+                    at = hdr - _Slot.dtw_table(B, cep is not None)
+                    vals = (2 if cep is None else 4) * B
                     if pathed:
                         path_rows = dict(zip(paths.MEMBERS, (out["duration_rounded"],) + tuple(
-                            model.mel_dtw_paths(out, ref, ref_lens, out=slot.dev[at:at + 2 * B])[2:])))
+                            model.mel_dtw_paths(out, ref, ref_lens, out=slot.dev[at:at + vals], cepstra=cep)[2:5])))
                     else:
-                        model.mel_dtw(out, ref, ref_lens, out=slot.dev[at:at + 2 * B])
+                        model.mel_dtw(out, ref, ref_lens, out=slot.dev[at:at + vals], cepstra=cep)
                 if aligned:
                     tab = _Slot.table(B)
                     H.pack_rows([(rows[name], out["src_lens" if level == "phone" else "tgt_lens"],

@@ -764,6 +764,24 @@ int fs2hip_dtw_dirs(const float* cost, const int* lens1, const int* lens2, float
 int fs2hip_dtw_path(const float* cost, const unsigned char* dirs, const int* lens1, const int* lens2, int* ref_first,
                     int* ref_last, float* frame_cost, int B, int T1, int T2, void* stream);
 
+/* Cepstral coefficients of frame sequences (csrc/cepstra.hip): the features `fs2l synthesize --compare-to DIR --cepstra K`
+ * and `fs2l train --val-synthesis --val-cepstra K` take the second DTW distance on (MCD-DTW's: the low DCT coefficients of
+ * a log-mel frame, the energy term dropped).  fp32, the lengths are read from device memory (clamped to 0 .. T here), no
+ * host synchronisation, no atomics and no workspace.
+ *   cepstra     x [B][T][C], table [K][C], out [B][T][K].  With n = clamp(lens[b], 0, T):
+ *                   out[b][t][k] = (((0.f + x[b][t][0] * table[k][0]) + x[b][t][1] * table[k][1]) + ...)   for t < n, k < K
+ *               in fp32 without contraction, m ascending, the same for every element whatever the tiling: bit-defined.
+ *               Rows t >= n of x are never read (they may hold NaN) and rows t >= n of out are never written; lens[b] = 0
+ *               writes nothing.  The table is the caller's (hip.dct_table: orthonormal DCT-II, rows 1 .. K,
+ *               table[k][m] = sqrt(2 / C) * cos(pi * (k + 1) * (m + 0.5) / C), float64 rounded to fp32).  A workgroup
+ *               stages 64 rows in LDS (odd row stride, a lane per row), its four wavefronts split the K coefficients and
+ *               read the table by uniform loads, and the 64 x K block of results leaves through the same LDS tile in one
+ *               contiguous piece.  1 <= C <= FS2_FRAME_DIST_MAX_C, 1 <= K <= min(C - 1, FS2_CEPSTRA_MAX_K).
+ * FS2HIP_EINVAL, before any launch: a null pointer, a non-positive extent, an extent beyond the limits above. */
+#define FS2_CEPSTRA_MAX_K 64
+int fs2hip_cepstra(const float* x, const int* lens, const float* table, float* out, int B, int T, int C, int K,
+                   void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Launch plans: a training step's whole launch sequence enqueued by ONE call.
  *
